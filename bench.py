@@ -9,6 +9,13 @@ Weak scaling: per-GPU microbatch fixed as N grows.
 Measures BASELINE.json's metric: tokens/sec (whole node), BLOOM-560M TP2xDP2
 (and BLOOM-7B1 TP2xPP2xDP2 via --model bloom-7b1, 1F1B pipeline + ZeRO-1),
 bf16, synthetic data, random-init weights.
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line (`ms_per_step` = wall time of one timed step).  Weights and token ids
+come from fixed seeds, so the same arguments give the same inputs on every
+run; `--dump-outputs DIR` stores what the last timed step produced so two
+builds can be compared.  `--full` is where any measurement beyond the
+headline figure belongs.
 """
 import argparse
 import json
@@ -63,7 +70,69 @@ def parse_args():
                    help="EXPERIMENTAL: also run the attention projection "
                         "GEMMs (qkv / output dense) in fp8")
     p.add_argument("--device", type=str, default=None)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step produced (loss, plus a fixed seeded sample of "
+                        "the updated parameters and their gradients) as "
+                        "DIR/<name>.npy in float32, for comparing two builds "
+                        "output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure; a plain run only sets up, warms up, times "
+                        "the steps and prints the result line (today the "
+                        "benchmark has no such extra measurements)")
     return p.parse_args()
+
+
+# --dump-outputs: at most this many sampled elements per dumped array
+# (2 arrays x 4M x 4 bytes = 32 MB, under the 64 MB a dump may take)
+DUMP_SAMPLE_ELEMS = 4 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, rank: int, loss, model):
+    """Write the last timed step's results as float32 .npy files.
+
+    `loss` is what the step returned; the step's other product is the
+    updated model, too large to store whole, so every parameter and its
+    gradient contribute elements at the same fixed, seeded, distinct
+    positions, the same share of each tensor, concatenated in
+    `named_parameters()` order.  Rank 0 writes `<name>.npy`, any other rank
+    `<name>.rank<r>.npy`."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, t):
+        arr = t.detach().to(device="cpu", dtype=torch.float32).numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+    if loss is not None:
+        save("loss", loss.reshape(1))
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    share = min(1.0, DUMP_SAMPLE_ELEMS / max(total, 1))
+    g = torch.Generator().manual_seed(20240)
+    p_parts, g_parts = [], []
+    for p in params:
+        n = p.numel()
+        if n == 0:
+            continue
+        k = n if share >= 1.0 else max(1, int(n * share))
+        # one seeded pick from each of k equal strides: distinct positions
+        stride = n // k
+        idx = torch.arange(k) * stride
+        if stride > 1:
+            idx = idx + torch.randint(0, stride, (k,), generator=g)
+        idx = idx.to(p.device)
+        p_parts.append(p.detach().reshape(-1)[idx].float().cpu())
+        # a parameter the step left without a gradient (another pipeline
+        # stage's, say) holds its place with zeros, so position i of
+        # grads_sample always belongs to position i of params_sample
+        g_parts.append(torch.zeros(k) if p.grad is None else
+                       p.grad.detach().reshape(-1)[idx].float().cpu())
+    save("params_sample", torch.cat(p_parts))
+    save("grads_sample", torch.cat(g_parts))
 
 
 def pick_parallelism(world_size: int, model: str, tp_arg: int, pp_arg: int, dp_arg: int):
@@ -266,8 +335,11 @@ def main():
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            one_step(set_to_none=False)
-        step_fn = graph.replay
+            graph_loss = one_step(set_to_none=False)
+
+        def step_fn():
+            graph.replay()
+            return graph_loss  # static buffer the replay just refilled
         torch.cuda.synchronize()
     else:
         for _ in range(args.warmup):
@@ -278,8 +350,9 @@ def main():
     if use_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_loss = None
     for _ in range(args.steps):
-        step_fn()
+        last_loss = step_fn()
     if use_gpu:
         torch.cuda.synchronize()
     if dist.is_initialized() and world_size > 1:
@@ -297,6 +370,15 @@ def main():
     tokens_per_step = global_batch * S
     tokens_per_sec = tokens_per_step * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last_loss, model)
+
+    if args.full:
+        # Measurements beyond the headline figure (other precisions or sizes,
+        # baselines, per-kernel figures) go here, after the timed window and
+        # the dump, so a plain run never pays for them.  None exist yet.
+        pass
 
     dtype_name = "bf16"
     if args.fp8_mlp or args.fp8_attn:

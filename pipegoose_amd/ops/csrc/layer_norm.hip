@@ -174,28 +174,40 @@ __global__ void layer_norm_bwd_dwdb_kernel(
     }
 }
 
-// stage 2: column-sum the [GY, H] partials.  blockIdx.y splits the GY
-// range (16 partials per block) so small H still spawns enough threads;
-// each column gets GY/16 atomics — negligible contention.
+// stage 2: column-sum the [GY, H] partials in a FIXED order, so dw/db are
+// bitwise reproducible from run to run (atomics combined them in arrival
+// order).  A block covers RED_COLS columns x RED_ROWS row groups so small H
+// still spawns enough threads: thread (c, r) adds partials r, r+RED_ROWS, ...
+// and the RED_ROWS group sums combine through LDS in index order.
+constexpr int RED_COLS = 32;
+constexpr int RED_ROWS = 8;
 __global__ void colsum_reduce_kernel(const float* __restrict__ part_w,
                                      const float* __restrict__ part_b,
                                      float* __restrict__ dw,
                                      float* __restrict__ db, int GY, int H) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= H) return;
-    const int g0 = blockIdx.y * 16;
-    const int g1 = min(g0 + 16, GY);
+    __shared__ float s_w[RED_ROWS][RED_COLS];
+    __shared__ float s_b[RED_ROWS][RED_COLS];
+    const int c = threadIdx.x % RED_COLS;
+    const int r = threadIdx.x / RED_COLS;
+    const int col = blockIdx.x * RED_COLS + c;
     float aw = 0.f, ab = 0.f;
-    for (int g = g0; g < g1; ++g) {
-        aw += part_w[(int64_t)g * H + col];
-        ab += part_b[(int64_t)g * H + col];
+    if (col < H) {
+        for (int g = r; g < GY; g += RED_ROWS) {
+            aw += part_w[(int64_t)g * H + col];
+            ab += part_b[(int64_t)g * H + col];
+        }
     }
-    if (gridDim.y == 1) {
+    s_w[r][c] = aw;
+    s_b[r][c] = ab;
+    __syncthreads();
+    if (r == 0 && col < H) {
+#pragma unroll
+        for (int k = 1; k < RED_ROWS; ++k) {
+            aw += s_w[k][c];
+            ab += s_b[k][c];
+        }
         dw[col] = aw;
         db[col] = ab;
-    } else {
-        atomicAdd(&dw[col], aw);
-        atomicAdd(&db[col], ab);
     }
 }
 
@@ -263,15 +275,18 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
     const int64_t H = x.size(-1);
     const int64_t N = x.numel() / H;
     auto dx = torch::empty_like(x);
-    auto dw = torch::zeros({H}, x.options().dtype(torch::kFloat));
-    auto db = torch::zeros({H}, x.options().dtype(torch::kFloat));
+    // dwdb: fill the chip (256 CUs, >=2 blocks/CU) with row-strided blocks;
+    // the vectorized path combines its partials in a fixed order (stage 2)
+    // and stores every column; only the scalar fallback (H % 8 != 0) still
+    // accumulates with fp32 atomics and needs dw/db zeroed.
+    const bool vec = (H % 8 == 0);
+    const auto f32 = x.options().dtype(torch::kFloat);
+    auto dw = vec ? torch::empty({H}, f32) : torch::zeros({H}, f32);
+    auto db = vec ? torch::empty({H}, f32) : torch::zeros({H}, f32);
     torch::Tensor part_w, part_b;
 
     constexpr int BLOCK = 256;
     auto stream = at::cuda::getCurrentCUDAStream();
-    // dwdb: fill the chip (256 CUs, >=2 blocks/CU) with row-strided blocks;
-    // fp32 atomics combine partials (512 adds/column max — low contention).
-    const bool vec = (H % 8 == 0);
     const int64_t cols = vec ? H / 8 : H;
     int grid_y = (int)std::min<int64_t>(N, 256);
     dim3 grid_dw((cols + BLOCK - 1) / BLOCK, grid_y);
@@ -279,7 +294,8 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
         part_w = torch::empty({grid_y, H}, x.options().dtype(torch::kFloat));
         part_b = torch::empty({grid_y, H}, x.options().dtype(torch::kFloat));
     }
-    dim3 grid_red((H + BLOCK - 1) / BLOCK, (grid_y + 15) / 16);
+    static_assert(BLOCK == RED_COLS * RED_ROWS, "colsum_reduce block shape");
+    dim3 grid_red((H + RED_COLS - 1) / RED_COLS);
 
     if (x.scalar_type() == torch::kBFloat16) {
         hipLaunchKernelGGL((layer_norm_bwd_dx_kernel<__hip_bfloat16, BLOCK>), dim3(N), dim3(BLOCK), 0, stream,

@@ -55,6 +55,42 @@ def test_layer_norm_bwd(dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("N,H", [(300, 40), (4096, 1024)])
+def test_layer_norm_bwd_dwdb_reproducible(N, H, dtype):
+    """Weight/bias grads come from a fixed-order two-stage column sum: they
+    repeat bitwise, and match a float64 sum.  (300, 40): rows uneven over the
+    256 partial rows, last reduce block only partly filled; (4096, 1024): the
+    flagship hidden size, 16 rows per partial.
+
+    Bound: every column sum runs through ceil(N/256) adds per partial, then
+    256/8 + 8 to combine them: 42 adds for N=300, 56 for N=4096.  With
+    mean/rstd/xhat carrying a few fp32 ulps per term, for both cases
+    |err| <= 128 * 2^-24 * sum|terms|; a bf16 result adds its own rounding,
+    2^-8 * |ref|."""
+    ext = _ext()
+    torch.manual_seed(6)
+    x = torch.randn(N, H, device="cuda", dtype=dtype)
+    w = torch.randn(H, device="cuda", dtype=dtype)
+    b = torch.randn(H, device="cuda", dtype=dtype)
+    dy = torch.randn(N, H, device="cuda", dtype=dtype)
+    _, mean, rstd = ext.layer_norm_fwd(x, w, b, 1e-5)
+    _, dw, db = ext.layer_norm_bwd(dy, x, w, mean, rstd)
+    for _ in range(3):
+        _, dw2, db2 = ext.layer_norm_bwd(dy, x, w, mean, rstd)
+        assert torch.equal(dw, dw2) and torch.equal(db, db2)
+
+    xd, dyd = x.double(), dy.double()
+    var, mu = torch.var_mean(xd, dim=-1, unbiased=False, keepdim=True)
+    terms_w = dyd * (xd - mu) * torch.rsqrt(var + 1e-5)
+    cast = 2.0 ** -8 if dtype == torch.bfloat16 else 0.0
+    for got, terms in ((dw, terms_w), (db, dyd)):
+        ref = terms.sum(0)
+        bound = 128 * 2.0 ** -24 * terms.abs().sum(0) + cast * ref.abs()
+        err = (got.double() - ref).abs()
+        assert (err <= bound).all(), (err / bound).max()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_bias_gelu(dtype):
     ext = _ext()
     torch.manual_seed(2)

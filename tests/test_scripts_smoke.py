@@ -15,8 +15,11 @@ def _run(args, timeout=240):
     return r.stdout
 
 
-def test_full_training_loop_example():
-    out = _run(["examples/full_training_loop.py", "--tiny", "--steps", "2"])
+def test_full_training_loop_example(tmp_path):
+    # checkpoints go to the test's own directory, not the example's shared
+    # default, which another user on the machine may own
+    out = _run(["examples/full_training_loop.py", "--tiny", "--steps", "2",
+                "--ckpt-dir", str(tmp_path / "ckpt")])
     assert "done: step 2" in out
 
 
@@ -31,6 +34,42 @@ def test_decode_bench_tool():
                 "--batch", "2", "--prompt-len", "16", "--new-tokens", "4",
                 "--graph"])
     assert "graph decode" in out
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the result line keeps its fields, the dump is
+    float32 .npy of the last timed step, and a second run with the same
+    arguments reproduces it exactly: same seeded inputs, and no kernel on the
+    training step sums in a run-dependent order."""
+    import json
+
+    import numpy as np
+
+    def run(sub):
+        out = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                    "--model", "bloom-tiny", "--seq-len", "128",
+                    "--micro-batch", "2", "--dump-outputs", str(tmp_path / sub)])
+        # the result line is the one JSON line (RCCL may print after it)
+        line, = [ln for ln in out.splitlines() if ln.startswith("{")]
+        return json.loads(line)
+
+    res = run("a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                "ms_per_step"):
+        assert key in res, res
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    run("b")
+    dumps = {}
+    for sub in ("a", "b"):
+        for name in ("loss", "params_sample", "grads_sample"):
+            arr = np.load(tmp_path / sub / f"{name}.npy")
+            assert arr.dtype == np.float32 and np.isfinite(arr).all(), name
+            dumps[sub, name] = arr
+    assert dumps["a", "params_sample"].shape == dumps["a", "grads_sample"].shape
+    total = sum(a.nbytes for (sub, _), a in dumps.items() if sub == "a")
+    assert total <= 64 * 2 ** 20
+    for name in ("loss", "params_sample", "grads_sample"):
+        np.testing.assert_array_equal(dumps["a", name], dumps["b", name], name)
 
 
 def test_moe_training_example():
