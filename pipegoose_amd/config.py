@@ -46,7 +46,7 @@ class RuntimeConfig:
     attn_v2: int = 1                  # 0 forces the v1 forward
     attn_bwd_v2: int = 1              # 0 forces the v1 backward
     attn_w4: int = 0                  # 1 forces 4-wave attention WGs (A/B)
-    moe_grouped: int = 0              # 1 routes mask-MoE through the bank
+    moe_grouped: int = 0              # 1 = padded bmm bank, 2 = HIP grouped GEMM
     hand_gemm: int = 0                # 1 forces the hand MFMA GEMM
     bgelu_rows: int = 1024            # bias-gelu bwd grid rows
     disable_ext: int = 0              # 1 disables the HIP extension

@@ -81,15 +81,19 @@ class Experts(nn.Module):
                                           weight).reshape(shape)
         k = 1 if dispatch_order.dim() == 1 else dispatch_order.size(-1)
         order2d = dispatch_order.reshape(-1, k)
-        import os
-        if self._grouped is not None and os.environ.get("PG_MOE_GROUPED") == "1":
+        mode = _grouped_mode()
+        if self._grouped is not None and mode in ("1", "2"):
             # measured SLOWER than the per-expert loop on the 1b7-MoE bench
             # (16.5k vs 41.3k tok/s): the ROCm transposed-bmm fault forces
             # contiguous weight copies every call (grouped.py), which
             # dominate.  Kept opt-in for re-evaluation when the backend bug
             # is fixed; the a2a path still uses the grouped bank (tokens/ep
             # per rank makes the copies proportionally cheaper there).
-            outputs = self._forward_local_grouped(flat, order2d, weight)
+            # PG_MOE_GROUPED=2 runs the same dispatch through the native
+            # grouped kernels instead (no padding, no weight copies; 47.9k
+            # tok/s on that bench, profiles/moe_grouped_gemm.md).
+            outputs = self._forward_local_grouped(
+                flat, order2d, weight, impl="hip" if mode == "2" else "bmm")
             if self.enable_tensor_parallel:
                 outputs = _AllReduceCombine.apply(outputs,
                                                   self.parallel_context)
@@ -128,7 +132,8 @@ class Experts(nn.Module):
 
     def _forward_local_grouped(self, flat: torch.Tensor,
                                order2d: torch.Tensor,
-                               weight: torch.Tensor = None) -> torch.Tensor:
+                               weight: torch.Tensor = None,
+                               impl: str = "bmm") -> torch.Tensor:
         """Mask-dispatch semantics via one grouped GEMM over the tokens
         routed to THIS rank's experts (all of them when EP is off)."""
         from pipegoose_amd.nn.expert_parallel.grouped import (
@@ -145,11 +150,15 @@ class Experts(nn.Module):
         tok, ridx = tok[keep], ridx[keep] - self.expert_offset
         perm = torch.argsort(ridx, stable=True)
         tok, ridx = tok[perm], ridx[perm]
-        counts = torch.bincount(ridx,
-                                minlength=self.num_local_experts).tolist()
+        counts = torch.bincount(ridx, minlength=self.num_local_experts)
         w1, b1, w2, b2, act = self._grouped
-        expert_out = grouped_mlp_forward(flat[tok], counts, w1, b1, w2, b2,
-                                         act).to(flat.dtype)
+        if impl == "hip":  # device offsets: no host sync on the counts
+            expert_out = grouped_mlp_forward(
+                flat[tok], None, w1, b1, w2, b2, act, impl="hip",
+                offsets=_offsets_from_counts(counts)).to(flat.dtype)
+        else:
+            expert_out = grouped_mlp_forward(flat[tok], counts.tolist(), w1,
+                                             b1, w2, b2, act).to(flat.dtype)
         if weight is not None:
             expert_out = expert_out * wvals[keep][perm].unsqueeze(-1) \
                 .to(flat.dtype)
@@ -214,8 +223,17 @@ class Experts(nn.Module):
 
         recv, local_idx, state = self._dispatcher.dispatch(send_tokens,
                                                            send_routes)
-        counts = torch.bincount(local_idx, minlength=self.num_local_experts).tolist()
-        if self._grouped is not None and recv.size(0) > 0:
+        counts = torch.bincount(local_idx, minlength=self.num_local_experts)
+        use_hip = self._grouped is not None and _grouped_mode() == "2"
+        counts = counts if use_hip else counts.tolist()
+        if use_hip:  # device offsets: no host sync on the counts
+            from pipegoose_amd.nn.expert_parallel.grouped import (
+                grouped_mlp_forward)
+            w1, b1, w2, b2, act = self._grouped
+            expert_out = grouped_mlp_forward(
+                recv, None, w1, b1, w2, b2, act, impl="hip",
+                offsets=_offsets_from_counts(counts)).to(recv.dtype)
+        elif self._grouped is not None and recv.size(0) > 0:
             from pipegoose_amd.nn.expert_parallel.grouped import (
                 grouped_mlp_forward)
             w1, b1, w2, b2, act = self._grouped
@@ -244,6 +262,21 @@ class Experts(nn.Module):
                                         accumulate=True)
                 combined = out32.to(chunk.dtype)
         return _Gather.apply(combined, 0, self.parallel_context)
+
+
+def _grouped_mode() -> str:
+    """PG_MOE_GROUPED: unset/0 = per-expert loop, 1 = padded bmm bank,
+    2 = native grouped-GEMM kernels."""
+    import os
+    return os.environ.get("PG_MOE_GROUPED", "0")
+
+
+def _offsets_from_counts(counts: torch.Tensor) -> torch.Tensor:
+    """[E] device counts -> int32 [E+1] segment bounds, no host sync."""
+    offsets = torch.zeros(counts.numel() + 1, device=counts.device,
+                          dtype=torch.int32)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return offsets
 
 
 class _AllReduceCombine(torch.autograd.Function):

@@ -1,18 +1,32 @@
-"""Grouped expert GEMM: all local experts' FFNs as ONE batched MFMA GEMM.
+"""Grouped expert FFN: all local experts over one expert-sorted buffer.
 
-The per-expert loop launches E small GEMMs that each underfill the 256-CU
-chip; here the expert-sorted token buffer (the all-to-all dispatch already
-produces it) is padded per expert to a common row count and the whole bank
-runs as two ``torch.bmm`` calls ([E, maxN, H] x [E, H, I]) — hipBLASLt
-batched MFMA kernels — with the activation between.  North-star item
-"grouped expert GEMM" (BASELINE.json): batching beats hand-tiling here
-because hipBLASLt's batched kernels already reach the MFMA roofline for
-these shapes; a hand kernel must match it or fall back (guide §5 rule).
+The per-expert loop launches E small GEMMs (plus mask, gather and
+``index_put``) that each underfill the 256-CU chip.  ``grouped_mlp_forward``
+runs the whole bank of identical ``Sequential(Linear, act, Linear)`` experts
+on the expert-sorted token buffer instead, with two implementations:
+
+``impl="hip"``
+    ``grouped_linear -> act -> grouped_linear`` (ops/grouped_gemm.py): one
+    hand-written MFMA kernel per pass (csrc/grouped_gemm.hip) that walks the
+    ragged segments unpadded and reads every expert's ``[N,K]`` weight in
+    place.  No ``zeros``/pad, no ``stack``, no ``cat``, no host sync; takes
+    device ``offsets`` instead of a Python ``counts`` list.  The activation
+    stays one elementwise torch op on the unpadded ``[T, I]`` buffer.
+
+``impl="bmm"``
+    the earlier batched path: every segment padded to the largest expert's
+    row count, all weights stacked per call, two ``torch.bmm`` with
+    contiguous transposed weight copies on both passes (the ROCm batched
+    GEMM faults on batch-strided operands, tools/moe_repro.py).  Those
+    copies are why it measured slower than the loop (16.5k vs 41.3k tok/s
+    on bloom-1b7 with 8 experts); it is kept for comparison.
+
+Measurements of both against the loop: profiles/moe_grouped_gemm.md.
 
 MI355X-native replacement for the reference's per-expert Python loop
 (nn/expert_parallel/experts.py:41-82; SURVEY §2.5 'grouped-GEMM HIP kernel').
 """
-from typing import List
+from typing import List, Optional
 
 import torch
 from torch import nn
@@ -68,11 +82,35 @@ class _GroupedLinear(torch.autograd.Function):
         return dx, dW
 
 
-def grouped_mlp_forward(tokens: torch.Tensor, counts: List[int],
+def grouped_mlp_hip(tokens: torch.Tensor, offsets: torch.Tensor,
+                    w1: List[torch.Tensor], b1, w2: List[torch.Tensor], b2,
+                    act: nn.Module) -> torch.Tensor:
+    """tokens: [N, H] sorted by local expert; offsets: int32 [E+1] device
+    tensor of segment bounds.  Returns [N, H_out] in the same order."""
+    from pipegoose_amd.ops.grouped_gemm import grouped_linear
+    h = grouped_linear(tokens, offsets, w1,
+                       None if b1[0] is None else b1)
+    h = act(h)
+    return grouped_linear(h, offsets, w2, None if b2[0] is None else b2)
+
+
+def grouped_mlp_forward(tokens: torch.Tensor, counts: Optional[List[int]],
                         w1: List[torch.Tensor], b1, w2: List[torch.Tensor],
-                        b2, act: nn.Module) -> torch.Tensor:
+                        b2, act: nn.Module, impl: str = "bmm",
+                        offsets: Optional[torch.Tensor] = None
+                        ) -> torch.Tensor:
     """tokens: [N, H] sorted by local expert with ``counts[i]`` rows each.
-    Returns [N, H_out] in the same order.  Differentiable (stack + bmm)."""
+    Returns [N, H_out] in the same order.  Differentiable.
+
+    ``impl="bmm"`` (stack + pad + bmm) needs the Python ``counts`` list;
+    ``impl="hip"`` needs the device ``offsets`` tensor instead (``counts``
+    is ignored and may be None)."""
+    if impl == "hip":
+        if offsets is None:
+            raise ValueError("grouped_mlp_forward(impl='hip') needs offsets")
+        return grouped_mlp_hip(tokens, offsets, w1, b1, w2, b2, act)
+    if impl != "bmm":
+        raise ValueError(f"unknown grouped impl {impl!r}")
     E = len(counts)
     H = tokens.size(-1)
     max_n = max(max(counts), 1)

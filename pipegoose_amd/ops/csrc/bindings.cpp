@@ -57,6 +57,18 @@ std::vector<torch::Tensor> silu_mul_bwd(torch::Tensor dy, torch::Tensor gate,
 std::vector<torch::Tensor> fp8_quant(torch::Tensor x, bool e5m2);
 std::vector<torch::Tensor> fp8_quant_dual(torch::Tensor x, bool e5m2);
 torch::Tensor fp8_transpose(torch::Tensor q);
+torch::Tensor grouped_gemm_fwd(torch::Tensor X,
+                               std::vector<torch::Tensor> weights,
+                               torch::Tensor offsets,
+                               c10::optional<torch::Tensor> bias);
+torch::Tensor grouped_gemm_dgrad(torch::Tensor dY,
+                                 std::vector<torch::Tensor> weights,
+                                 torch::Tensor offsets);
+std::vector<torch::Tensor> grouped_gemm_wgrad(torch::Tensor dY,
+                                              torch::Tensor X,
+                                              torch::Tensor offsets,
+                                              int64_t E,
+                                              bool want_bias_grad);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("layer_norm_fwd", &layer_norm_fwd, "fused LayerNorm forward (gfx950)");
@@ -103,4 +115,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "LDS-tiled byte transpose for fp8 GEMM operand layouts");
     m.def("silu_mul_fwd", &silu_mul_fwd, "fused SwiGLU silu(g)*u (gfx950)");
     m.def("silu_mul_bwd", &silu_mul_bwd, "fused SwiGLU backward (gfx950)");
+    m.def("grouped_gemm_fwd", &grouped_gemm_fwd,
+          "grouped expert GEMM Y[r] = X[r] @ W[e]^T (+b[e]) over an "
+          "expert-sorted ragged buffer (gfx950 MFMA)",
+          py::arg("X"), py::arg("weights"), py::arg("offsets"),
+          py::arg("bias") = c10::nullopt);
+    m.def("grouped_gemm_dgrad", &grouped_gemm_dgrad,
+          "grouped expert GEMM input grad dX[r] = dY[r] @ W[e] (gfx950 MFMA)");
+    m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad,
+          "grouped expert GEMM weight/bias grads, deterministic: "
+          "dW[e] = dY_e^T @ X_e, db[e] = colsum(dY_e) (gfx950 MFMA)");
 }

@@ -26,6 +26,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/adamw.hip",
     "pipegoose_amd/ops/csrc/gemm.hip",
     "pipegoose_amd/ops/csrc/fp8_quant.hip",
+    "pipegoose_amd/ops/csrc/grouped_gemm.hip",
 ]
 
 setup(
