@@ -8,6 +8,9 @@ MI355X path: when every rank holds >1 expert the local experts run as a
 grouped GEMM (one kernel for all local experts) via pipegoose_amd.ops; the
 cross-rank combine stays a single RCCL all-reduce over xGMI.  Token
 all-to-all dispatch is used by the EP=8 config (see expert_parallel.py).
+With PG_MOE_GROUPED=3 an unsharded bank also dispatches and combines with
+kernels (ops/moe_permute.py): the layer runs forward and backward without
+a host synchronisation.
 """
 import copy
 
@@ -82,7 +85,7 @@ class Experts(nn.Module):
         k = 1 if dispatch_order.dim() == 1 else dispatch_order.size(-1)
         order2d = dispatch_order.reshape(-1, k)
         mode = _grouped_mode()
-        if self._grouped is not None and mode in ("1", "2"):
+        if self._grouped is not None and mode in ("1", "2", "3"):
             # measured SLOWER than the per-expert loop on the 1b7-MoE bench
             # (16.5k vs 41.3k tok/s): the ROCm transposed-bmm fault forces
             # contiguous weight copies every call (grouped.py), which
@@ -92,8 +95,18 @@ class Experts(nn.Module):
             # PG_MOE_GROUPED=2 runs the same dispatch through the native
             # grouped kernels instead (no padding, no weight copies; 47.9k
             # tok/s on that bench, profiles/moe_grouped_gemm.md).
+            # PG_MOE_GROUPED=3 additionally replaces the eager dispatch and
+            # combine around those kernels (two host syncs, an argsort, an
+            # fp32 [N,H] atomic index_put for top-k) by the routing-plan,
+            # permute and combine kernels of ops/moe_permute.py: no host
+            # sync in forward or backward, deterministic.  Where that path
+            # does not apply (CPU, fp32, odd shapes, expert-sharded bank)
+            # mode 3 is mode 2.
+            if mode == "3" and self._fused_applies(flat, weight):
+                return self._forward_local_fused(flat, order2d,
+                                                 weight).reshape(shape)
             outputs = self._forward_local_grouped(
-                flat, order2d, weight, impl="hip" if mode == "2" else "bmm")
+                flat, order2d, weight, impl="bmm" if mode == "1" else "hip")
             if self.enable_tensor_parallel:
                 outputs = _AllReduceCombine.apply(outputs,
                                                   self.parallel_context)
@@ -173,6 +186,54 @@ class Experts(nn.Module):
         out32 = out32.index_put((tok,), expert_out.float(), accumulate=True)
         return out32.to(flat.dtype)
 
+    def _fused_applies(self, flat: torch.Tensor, weight) -> bool:
+        """PG_MOE_GROUPED=3 takes the call: local (unsharded) bank, rows the
+        permute kernels and both grouped linears accept natively."""
+        from pipegoose_amd.ops import grouped_gemm, moe_permute
+        if self._grouped is None or self.enable_tensor_parallel:
+            return False
+        w1, _, w2, _, _ = self._grouped
+        if weight is not None and (
+                not weight.is_cuda
+                or weight.dtype not in (torch.bfloat16, torch.float32)):
+            return False
+        if not moe_permute.supported(flat, self.num_local_experts):
+            return False
+        if not grouped_gemm.supported(flat, w1):
+            return False
+        I, H_out = w1[0].size(0), w2[0].size(0)
+        # the second linear sees [S, I] rows; the combine moves [S, H_out]
+        return (H_out % 8 == 0 and all(
+            w.is_cuda and w.dtype == torch.bfloat16
+            and tuple(w.shape) == (H_out, I) for w in w2)
+            and I % 64 == 0 and H_out % 128 == 0)
+
+    def _forward_local_fused(self, flat: torch.Tensor, order2d: torch.Tensor,
+                             weight: torch.Tensor = None) -> torch.Tensor:
+        """The mask-dispatch semantics of ``_forward_local_grouped`` with no
+        host synchronisation: the routing plan, the gather into the
+        expert-sorted buffer and the gate-weighted combine are kernels
+        (ops/moe_permute.py).  The buffer always has N*k rows; rows past
+        ``offsets[E]`` are dead -- the grouped kernels walk only the rows
+        ``offsets`` covers, and permute/combine go through the plan."""
+        from pipegoose_amd.nn.expert_parallel.grouped import (
+            grouped_mlp_forward)
+        from pipegoose_amd.ops.moe_permute import (combine, permute,
+                                                   route_plan)
+        N = order2d.size(0)
+        plan = route_plan(order2d, weight, self.expert_offset,
+                          self.num_local_experts)
+        xs = permute(flat, plan)                           # [N*k, H]
+        w1, b1, w2, b2, act = self._grouped
+        ys = grouped_mlp_forward(xs, None, w1, b1, w2, b2, act, impl="hip",
+                                 offsets=plan.offsets).to(flat.dtype)
+        gates = None
+        if weight is not None:
+            # tiny [N,k] gather; its autograd carries dgate into `weight`
+            gates = weight.reshape(N, self.num_experts) \
+                .gather(1, order2d).reshape(-1).float()
+        return combine(ys, gates, plan)
+
     def _forward_alltoall(self, flat: torch.Tensor,
                           dispatch_order: torch.Tensor,
                           weight: torch.Tensor = None):
@@ -224,7 +285,8 @@ class Experts(nn.Module):
         recv, local_idx, state = self._dispatcher.dispatch(send_tokens,
                                                            send_routes)
         counts = torch.bincount(local_idx, minlength=self.num_local_experts)
-        use_hip = self._grouped is not None and _grouped_mode() == "2"
+        # mode 3 is mode 2 here: the split sizes need the host anyway
+        use_hip = self._grouped is not None and _grouped_mode() in ("2", "3")
         counts = counts if use_hip else counts.tolist()
         if use_hip:  # device offsets: no host sync on the counts
             from pipegoose_amd.nn.expert_parallel.grouped import (
@@ -266,7 +328,9 @@ class Experts(nn.Module):
 
 def _grouped_mode() -> str:
     """PG_MOE_GROUPED: unset/0 = per-expert loop, 1 = padded bmm bank,
-    2 = native grouped-GEMM kernels."""
+    2 = native grouped-GEMM kernels, 3 = those plus the sync-free
+    routing-plan/permute/combine kernels around them (mode 2 wherever the
+    fused path does not apply)."""
     import os
     return os.environ.get("PG_MOE_GROUPED", "0")
 

@@ -69,6 +69,22 @@ std::vector<torch::Tensor> grouped_gemm_wgrad(torch::Tensor dY,
                                               torch::Tensor offsets,
                                               int64_t E,
                                               bool want_bias_grad);
+std::vector<torch::Tensor> moe_route_plan(torch::Tensor order,
+                                          c10::optional<torch::Tensor> weight,
+                                          int64_t e0, int64_t E);
+torch::Tensor moe_permute_fwd(torch::Tensor x, torch::Tensor slot_of_row,
+                              int64_t k);
+torch::Tensor moe_permute_bwd(torch::Tensor dxs, torch::Tensor row_of_slot,
+                              int64_t N, int64_t k);
+torch::Tensor moe_combine_fwd(torch::Tensor ys,
+                              c10::optional<torch::Tensor> gates,
+                              torch::Tensor row_of_slot, int64_t N,
+                              int64_t k);
+std::vector<torch::Tensor> moe_combine_bwd(torch::Tensor dout,
+                                           torch::Tensor ys,
+                                           c10::optional<torch::Tensor> gates,
+                                           torch::Tensor slot_of_row,
+                                           int64_t k, bool want_dgate);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("layer_norm_fwd", &layer_norm_fwd, "fused LayerNorm forward (gfx950)");
@@ -125,4 +141,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad,
           "grouped expert GEMM weight/bias grads, deterministic: "
           "dW[e] = dY_e^T @ X_e, db[e] = colsum(dY_e) (gfx950 MFMA)");
+    m.def("moe_route_plan", &moe_route_plan,
+          "MoE routing plan: stable counting sort of the kept slots by "
+          "local expert -> (offsets, row_of_slot, slot_of_row); no host "
+          "sync, no atomics (gfx950)");
+    m.def("moe_permute_fwd", &moe_permute_fwd,
+          "gather token rows into the expert-sorted buffer (gfx950)");
+    m.def("moe_permute_bwd", &moe_permute_bwd,
+          "sum a token's expert-sorted grad rows, fp32, no atomics (gfx950)");
+    m.def("moe_combine_fwd", &moe_combine_fwd,
+          "gate-weighted sum of a token's expert output rows (gfx950)");
+    m.def("moe_combine_bwd", &moe_combine_bwd,
+          "combine backward: dys and dgate from one read of dout (gfx950)");
 }

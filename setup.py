@@ -27,6 +27,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/gemm.hip",
     "pipegoose_amd/ops/csrc/fp8_quant.hip",
     "pipegoose_amd/ops/csrc/grouped_gemm.hip",
+    "pipegoose_amd/ops/csrc/moe_permute.hip",
 ]
 
 setup(
