@@ -38,7 +38,7 @@ class ExpertParallel(Parallel):
         self.enable_tensor_parallel = enable_tensor_parallel
 
     def parallelize(self) -> nn.Module:
-        pattern = re.compile(r"^(?:transformer\.)?(?:h|layers)\.(\d+)\.mlp$", re.IGNORECASE)
+        pattern = re.compile(r"^(?:transformer\.|model\.)?(?:h|layers)\.(\d+)\.mlp$", re.IGNORECASE)
         replaced = 0
         for name, module in list(self.module.named_modules()):
             m = pattern.search(name)

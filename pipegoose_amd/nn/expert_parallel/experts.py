@@ -65,8 +65,12 @@ class Experts(nn.Module):
             setattr(p, "is_expert", True)
         # grouped-GEMM fast path: identical Sequential(Linear, act, Linear)
         # experts run as one batched MFMA GEMM over the expert-sorted tokens
-        from pipegoose_amd.nn.expert_parallel.grouped import match_grouped_mlp
+        from pipegoose_amd.nn.expert_parallel.grouped import (
+            match_grouped_glu, match_grouped_mlp)
         self._grouped = match_grouped_mlp(self.experts)
+        # identical GatedExpertMLP experts: the gated bank of the native
+        # kernels (PG_MOE_GROUPED=2/3); the bmm bank has no gated form
+        self._grouped_glu = match_grouped_glu(self.experts)
 
     def forward(self, inputs: torch.Tensor, dispatch_order: torch.Tensor,
                 weight: torch.Tensor = None, *args, **kwargs):
@@ -85,7 +89,7 @@ class Experts(nn.Module):
         k = 1 if dispatch_order.dim() == 1 else dispatch_order.size(-1)
         order2d = dispatch_order.reshape(-1, k)
         mode = _grouped_mode()
-        if self._grouped is not None and mode in ("1", "2", "3"):
+        if self._bank_modes(mode):
             # measured SLOWER than the per-expert loop on the 1b7-MoE bench
             # (16.5k vs 41.3k tok/s): the ROCm transposed-bmm fault forces
             # contiguous weight copies every call (grouped.py), which
@@ -143,6 +147,27 @@ class Experts(nn.Module):
             outputs = _AllReduceCombine.apply(outputs, self.parallel_context)
         return outputs.reshape(shape)
 
+    def _bank_modes(self, mode: str) -> bool:
+        """Whether PG_MOE_GROUPED=`mode` runs the experts as one bank:
+        Sequential(Linear, act, Linear) experts in modes 1-3, gated experts
+        in modes 2 and 3 (native kernels only)."""
+        if self._grouped is not None:
+            return mode in ("1", "2", "3")
+        return self._grouped_glu is not None and mode in ("2", "3")
+
+    def _bank_hip(self, tokens: torch.Tensor,
+                  offsets: torch.Tensor) -> torch.Tensor:
+        """The whole local bank over an expert-sorted buffer through the
+        native grouped kernels: tokens [S, H], device offsets [E+1]."""
+        from pipegoose_amd.nn.expert_parallel.grouped import (
+            grouped_glu_mlp_forward, grouped_mlp_forward)
+        if self._grouped is not None:
+            w1, b1, w2, b2, act = self._grouped
+            return grouped_mlp_forward(tokens, None, w1, b1, w2, b2, act,
+                                       impl="hip", offsets=offsets)
+        wg, wu, wd = self._grouped_glu
+        return grouped_glu_mlp_forward(tokens, offsets, wg, wu, wd)
+
     def _forward_local_grouped(self, flat: torch.Tensor,
                                order2d: torch.Tensor,
                                weight: torch.Tensor = None,
@@ -164,12 +189,11 @@ class Experts(nn.Module):
         perm = torch.argsort(ridx, stable=True)
         tok, ridx = tok[perm], ridx[perm]
         counts = torch.bincount(ridx, minlength=self.num_local_experts)
-        w1, b1, w2, b2, act = self._grouped
         if impl == "hip":  # device offsets: no host sync on the counts
-            expert_out = grouped_mlp_forward(
-                flat[tok], None, w1, b1, w2, b2, act, impl="hip",
-                offsets=_offsets_from_counts(counts)).to(flat.dtype)
+            expert_out = self._bank_hip(
+                flat[tok], _offsets_from_counts(counts)).to(flat.dtype)
         else:
+            w1, b1, w2, b2, act = self._grouped
             expert_out = grouped_mlp_forward(flat[tok], counts.tolist(), w1,
                                              b1, w2, b2, act).to(flat.dtype)
         if weight is not None:
@@ -188,21 +212,26 @@ class Experts(nn.Module):
 
     def _fused_applies(self, flat: torch.Tensor, weight) -> bool:
         """PG_MOE_GROUPED=3 takes the call: local (unsharded) bank, rows the
-        permute kernels and both grouped linears accept natively."""
+        permute kernels and every grouped projection accept natively."""
         from pipegoose_amd.ops import grouped_gemm, moe_permute
-        if self._grouped is None or self.enable_tensor_parallel:
+        if self.enable_tensor_parallel or not self._bank_modes("3"):
             return False
-        w1, _, w2, _, _ = self._grouped
+        if self._grouped is not None:
+            w1, _, w2, _, _ = self._grouped
+            wu = None
+        else:  # gated bank: gate and up share the first projection's shape
+            w1, wu, w2 = self._grouped_glu
         if weight is not None and (
                 not weight.is_cuda
                 or weight.dtype not in (torch.bfloat16, torch.float32)):
             return False
         if not moe_permute.supported(flat, self.num_local_experts):
             return False
-        if not grouped_gemm.supported(flat, w1):
+        if not (grouped_gemm.supported(flat, w1) if wu is None
+                else grouped_gemm.supported_glu(flat, w1, wu)):
             return False
         I, H_out = w1[0].size(0), w2[0].size(0)
-        # the second linear sees [S, I] rows; the combine moves [S, H_out]
+        # the last linear sees [S, I] rows; the combine moves [S, H_out]
         return (H_out % 8 == 0 and all(
             w.is_cuda and w.dtype == torch.bfloat16
             and tuple(w.shape) == (H_out, I) for w in w2)
@@ -216,17 +245,13 @@ class Experts(nn.Module):
         (ops/moe_permute.py).  The buffer always has N*k rows; rows past
         ``offsets[E]`` are dead -- the grouped kernels walk only the rows
         ``offsets`` covers, and permute/combine go through the plan."""
-        from pipegoose_amd.nn.expert_parallel.grouped import (
-            grouped_mlp_forward)
         from pipegoose_amd.ops.moe_permute import (combine, permute,
                                                    route_plan)
         N = order2d.size(0)
         plan = route_plan(order2d, weight, self.expert_offset,
                           self.num_local_experts)
         xs = permute(flat, plan)                           # [N*k, H]
-        w1, b1, w2, b2, act = self._grouped
-        ys = grouped_mlp_forward(xs, None, w1, b1, w2, b2, act, impl="hip",
-                                 offsets=plan.offsets).to(flat.dtype)
+        ys = self._bank_hip(xs, plan.offsets).to(flat.dtype)
         gates = None
         if weight is not None:
             # tiny [N,k] gather; its autograd carries dgate into `weight`
@@ -286,15 +311,11 @@ class Experts(nn.Module):
                                                            send_routes)
         counts = torch.bincount(local_idx, minlength=self.num_local_experts)
         # mode 3 is mode 2 here: the split sizes need the host anyway
-        use_hip = self._grouped is not None and _grouped_mode() in ("2", "3")
+        use_hip = _grouped_mode() in ("2", "3") and self._bank_modes("2")
         counts = counts if use_hip else counts.tolist()
         if use_hip:  # device offsets: no host sync on the counts
-            from pipegoose_amd.nn.expert_parallel.grouped import (
-                grouped_mlp_forward)
-            w1, b1, w2, b2, act = self._grouped
-            expert_out = grouped_mlp_forward(
-                recv, None, w1, b1, w2, b2, act, impl="hip",
-                offsets=_offsets_from_counts(counts)).to(recv.dtype)
+            expert_out = self._bank_hip(
+                recv, _offsets_from_counts(counts)).to(recv.dtype)
         elif self._grouped is not None and recv.size(0) > 0:
             from pipegoose_amd.nn.expert_parallel.grouped import (
                 grouped_mlp_forward)

@@ -23,6 +23,13 @@ on the expert-sorted token buffer instead, with two implementations:
 
 Measurements of both against the loop: profiles/moe_grouped_gemm.md.
 
+Gated experts (``GatedExpertMLP``: ``down(silu(gate(x)) * up(x))``, the
+llama / Mixtral shape) have a bank of their own on the ``hip`` route only:
+``grouped_glu_mlp_forward`` is ``grouped_glu -> grouped_linear``
+(ops/grouped_gemm.py; the gate and up products and the activation can run
+as one kernel, opt-in -- profiles/moe_grouped_gemm.md §5).  There is no
+bmm form of it.
+
 MI355X-native replacement for the reference's per-expert Python loop
 (nn/expert_parallel/experts.py:41-82; SURVEY §2.5 'grouped-GEMM HIP kernel').
 """
@@ -33,6 +40,25 @@ from torch import nn
 
 
 _SUPPORTED_ACTS = (nn.GELU, nn.SiLU, nn.ReLU, nn.Tanh)
+
+
+class GatedExpertMLP(nn.Module):
+    """Dense gated (SwiGLU) expert: ``down_proj(silu(gate_proj(x)) *
+    up_proj(x))`` with three bias-free linears named as in the llama family
+    (models/llama.py::LlamaMLP).  A bank of identical ones runs on the
+    grouped and sync-free MoE paths (PG_MOE_GROUPED=2/3)."""
+
+    def __init__(self, hidden: int, intermediate: int,
+                 out: Optional[int] = None):
+        super().__init__()
+        out = hidden if out is None else out
+        self.gate_proj = nn.Linear(hidden, intermediate, bias=False)
+        self.up_proj = nn.Linear(hidden, intermediate, bias=False)
+        self.down_proj = nn.Linear(intermediate, out, bias=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from pipegoose_amd.ops.silu_mul import silu_mul
+        return self.down_proj(silu_mul(self.gate_proj(x), self.up_proj(x)))
 
 
 def match_grouped_mlp(experts: nn.ModuleList):
@@ -56,6 +82,39 @@ def match_grouped_mlp(experts: nn.ModuleList):
     if any(b is None for b in b1) != all(b is None for b in b1):
         return None
     return w1, b1, w2, b2, act
+
+
+def match_grouped_glu(experts: nn.ModuleList):
+    """If every expert is a GatedExpertMLP (three bias-free linears) of
+    identical shapes, return (w_gate, w_up, w_down) lists; else None."""
+    wg, wu, wd = [], [], []
+    for e in experts:
+        if not isinstance(e, GatedExpertMLP):
+            return None
+        lins = (e.gate_proj, e.up_proj, e.down_proj)
+        if not all(isinstance(m, nn.Linear) and m.bias is None
+                   for m in lins):
+            return None
+        wg.append(e.gate_proj.weight)
+        wu.append(e.up_proj.weight)
+        wd.append(e.down_proj.weight)
+    if not wg:
+        return None
+    for ws in (wg, wu, wd):
+        if any(w.shape != ws[0].shape for w in ws):
+            return None
+    if wu[0].shape != wg[0].shape or wd[0].size(1) != wg[0].size(0):
+        return None
+    return wg, wu, wd
+
+
+def grouped_glu_mlp_forward(tokens: torch.Tensor, offsets: torch.Tensor,
+                            wg: List[torch.Tensor], wu: List[torch.Tensor],
+                            wd: List[torch.Tensor]) -> torch.Tensor:
+    """tokens: [N, H] sorted by local expert; offsets: int32 [E+1] device
+    tensor of segment bounds.  Returns [N, H_out] in the same order."""
+    from pipegoose_amd.ops.grouped_gemm import grouped_glu, grouped_linear
+    return grouped_linear(grouped_glu(tokens, offsets, wg, wu), offsets, wd)
 
 
 class _GroupedLinear(torch.autograd.Function):

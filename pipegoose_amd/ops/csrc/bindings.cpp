@@ -69,6 +69,15 @@ std::vector<torch::Tensor> grouped_gemm_wgrad(torch::Tensor dY,
                                               torch::Tensor offsets,
                                               int64_t E,
                                               bool want_bias_grad);
+std::vector<torch::Tensor> grouped_glu_fwd(torch::Tensor X,
+                                           std::vector<torch::Tensor> w_gate,
+                                           std::vector<torch::Tensor> w_up,
+                                           torch::Tensor offsets,
+                                           bool save_gu);
+torch::Tensor grouped_glu_dgrad(torch::Tensor dG, torch::Tensor dU,
+                                std::vector<torch::Tensor> w_gate,
+                                std::vector<torch::Tensor> w_up,
+                                torch::Tensor offsets);
 std::vector<torch::Tensor> moe_route_plan(torch::Tensor order,
                                           c10::optional<torch::Tensor> weight,
                                           int64_t e0, int64_t E);
@@ -141,6 +150,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad,
           "grouped expert GEMM weight/bias grads, deterministic: "
           "dW[e] = dY_e^T @ X_e, db[e] = colsum(dY_e) (gfx950 MFMA)");
+    m.def("grouped_glu_fwd", &grouped_glu_fwd,
+          "gated expert bank forward: g = X @ Wg[e]^T, u = X @ Wu[e]^T and "
+          "h = silu(g) * u from one read of X -> (h, g, u) (gfx950 MFMA)",
+          py::arg("X"), py::arg("w_gate"), py::arg("w_up"),
+          py::arg("offsets"), py::arg("save_gu") = true);
+    m.def("grouped_glu_dgrad", &grouped_glu_dgrad,
+          "gated expert bank input grad dX[r] = dg[r] @ Wg[e] + du[r] @ "
+          "Wu[e], one fp32 accumulator, one rounding (gfx950 MFMA)");
     m.def("moe_route_plan", &moe_route_plan,
           "MoE routing plan: stable counting sort of the kept slots by "
           "local expert -> (offsets, row_of_slot, slot_of_row); no host "

@@ -73,6 +73,34 @@ __device__ __forceinline__ int clamp_off(int v, int T) {
     return v < 0 ? 0 : (v > T ? T : v);
 }
 
+// (expert, first row, live rows) of 128-row M-tile `mt`: tiles lie only
+// inside the clamped, monotone segments.  e < 0 marks a surplus block of
+// the host's grid bound.  Block-uniform.
+struct MTile {
+    int e, row0, rows_valid;
+};
+
+__device__ __forceinline__ MTile locate_m_tile(const int* __restrict__ offsets,
+                                               int mt, int T, int E) {
+    MTile t{-1, 0, 0};
+    int acc = 0;
+    int lo = clamp_off(offsets[0], T);
+    for (int i = 0; i < E; ++i) {
+        int hi = clamp_off(offsets[i + 1], T);
+        hi = hi > lo ? hi : lo;
+        const int tiles = (hi - lo + BM - 1) / BM;
+        if (mt < acc + tiles) {
+            t.e = i;
+            t.row0 = lo + (mt - acc) * BM;
+            t.rows_valid = hi - t.row0 < BM ? hi - t.row0 : BM;
+            break;
+        }
+        acc += tiles;
+        lo = hi;
+    }
+    return t;
+}
+
 // LDS bank swizzles.  global_load_lds writes lane-linear, so the images
 // are swizzled on the SOURCE side: LDS position (row, physical block p)
 // holds the tile's logical block p ^ f(row) of that row.
@@ -163,25 +191,8 @@ void grouped_gemm_kernel(const bf16* __restrict__ A, const WeightPtrs wp,
     const int mt = wgid / n_tiles_n;
     const int tn = wgid % n_tiles_n;
 
-    // locate (expert, row range) of M-tile `mt`; block-uniform
-    int e = -1, row0 = 0, rows_valid = 0;
-    {
-        int acc = 0;
-        int lo = clamp_off(offsets[0], T);
-        for (int i = 0; i < E; ++i) {
-            int hi = clamp_off(offsets[i + 1], T);
-            hi = hi > lo ? hi : lo;
-            const int tiles = (hi - lo + BM - 1) / BM;
-            if (mt < acc + tiles) {
-                e = i;
-                row0 = lo + (mt - acc) * BM;
-                rows_valid = hi - row0 < BM ? hi - row0 : BM;
-                break;
-            }
-            acc += tiles;
-            lo = hi;
-        }
-    }
+    const MTile t = locate_m_tile(offsets, mt, T, E);
+    const int e = t.e, row0 = t.row0, rows_valid = t.rows_valid;
     if (e < 0) return;  // surplus block of the host's upper bound
 
     __shared__ __attribute__((aligned(16))) bf16 a_t[2][BM * BK];
@@ -267,6 +278,233 @@ void grouped_gemm_kernel(const bf16* __restrict__ A, const WeightPtrs wp,
                 if (row < rows_valid) {
                     c_base[(int64_t)row * NOUT + col] =
                         (bf16)(acc[mf][nf][r] + bv);
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------- gated (GLU) bank
+// Gated experts: h = silu(x . Wg[e]^T) * (x . Wu[e]^T).
+//
+// Forward: a block owns 128 rows x 64 output columns and computes BOTH
+// products for them from one staged X tile.  Its 128-row B image holds the
+// 64 gate rows and the 64 up rows of the weights interleaved in groups of
+// 32 -- [g 0-31 | u 0-31 | g 32-63 | u 32-63] -- so wave column wn has gate
+// in fragments nf = 0,1 and up in nf = 2,3 for the same 32 output columns:
+// acc[mf][nf][r] and acc[mf][nf + 2][r] are the gate and the up value of
+// one output element, in the same lane.  The epilogue needs no LDS and no
+// cross-lane traffic.  Every element is accumulated by the MFMA sequence
+// grouped_gemm_kernel<false, 128, false> runs for it, so g and u are
+// bitwise the two plain forwards; h is formed from the ROUNDED g and u
+// with silu_mul.hip's formula, so the saved g, u define the forward exactly.
+__device__ __forceinline__ float glu_silu(float x) {
+    return x / (1.0f + __expf(-x));
+}
+
+template <bool SAVE_GU>
+__global__ __launch_bounds__(NTHREADS)
+void grouped_glu_fwd_kernel(const bf16* __restrict__ X, const WeightPtrs wg,
+                            const WeightPtrs wu,
+                            const int* __restrict__ offsets,
+                            bf16* __restrict__ H, bf16* __restrict__ G,
+                            bf16* __restrict__ U, int T, int E, int K, int I,
+                            int n_tiles_n) {
+    constexpr int BNO = 64;  // output columns per block
+    constexpr int SUB = 32;  // rows per gate / up sub-image
+    const int wgid = xcd_remap(blockIdx.x, gridDim.x);
+    const int mt = wgid / n_tiles_n;
+    const int tn = wgid % n_tiles_n;
+
+    const MTile t = locate_m_tile(offsets, mt, T, E);
+    const int e = t.e, row0 = t.row0, rows_valid = t.rows_valid;
+    if (e < 0) return;  // surplus block of the host's upper bound
+
+    __shared__ __attribute__((aligned(16))) bf16 a_t[2][BM * BK];
+    __shared__ __attribute__((aligned(16))) bf16 b_t[2][2 * BNO * BK];
+
+    const int tid = threadIdx.x;
+    const int wave = tid / WAVE_SIZE;
+    const int lane = tid % WAVE_SIZE;
+    const int lgrp = lane >> 4, lcol = lane & 15;
+    const int wr = wave >> 1, wn = wave & 1;  // 2x2 waves of 64 x (32g + 32u)
+
+    frag_cd acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = frag_cd{0.f, 0.f, 0.f, 0.f};
+
+    const int64_t col0 = (int64_t)tn * BNO;
+    const bf16* a_base = X + (int64_t)row0 * K;
+    const bf16* __restrict__ Wg = wg.w[e] + col0 * K;
+    const bf16* __restrict__ Wu = wu.w[e] + col0 * K;
+    auto stage = [&](int buf, int kt) {
+        const int64_t k0 = (int64_t)kt * BK;
+        stage_tile<BM, BK, false>(a_t[buf], a_base + k0, K, rows_valid - 1,
+                                  wave, lane);
+        // sub-images start at multiples of 32 rows: row_swz is unchanged
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            stage_tile<SUB, BK, false>(b_t[buf] + (2 * s) * SUB * BK,
+                                       Wg + (int64_t)s * SUB * K + k0, K,
+                                       SUB - 1, wave, lane);
+            stage_tile<SUB, BK, false>(b_t[buf] + (2 * s + 1) * SUB * BK,
+                                       Wu + (int64_t)s * SUB * K + k0, K,
+                                       SUB - 1, wave, lane);
+        }
+    };
+
+    const int n_kt = K / BK;
+    stage(0, 0);
+    __syncthreads();  // drains the glds (vmcnt(0))
+
+    int buf = 0;
+    for (int kt = 0; kt < n_kt; ++kt) {
+        if (kt + 1 < n_kt) stage(buf ^ 1, kt + 1);
+#pragma unroll
+        for (int kk = 0; kk < BK / 32; ++kk) {
+            frag_ab av[4];
+#pragma unroll
+            for (int mf = 0; mf < 4; ++mf) {
+                av[mf] = read_frag_row(a_t[buf], wr * 64 + mf * 16 + lcol,
+                                       kk * 4 + lgrp);
+            }
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int nf = 0; nf < 4; ++nf) {
+                const frag_ab bv = read_frag_row(
+                    b_t[buf], wn * 64 + nf * 16 + lcol, kk * 4 + lgrp);
+#pragma unroll
+                for (int mf = 0; mf < 4; ++mf) {
+                    acc[mf][nf] = MFMA16(av[mf], bv, acc[mf][nf]);
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    // epilogue: gate in nf, up in nf + 2; rows past the segment end are the
+    // next expert's and are never written
+    const int64_t out0 = (int64_t)row0 * I;
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf) {
+        const int64_t col = col0 + wn * SUB + nf * 16 + lcol;
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = wr * 64 + mf * 16 + 4 * lgrp + r;
+                if (row < rows_valid) {
+                    // "+ 0.f" is the bias-free forward's rounding input
+                    const bf16 g = (bf16)(acc[mf][nf][r] + 0.f);
+                    const bf16 u = (bf16)(acc[mf][nf + 2][r] + 0.f);
+                    const int64_t o = out0 + (int64_t)row * I + col;
+                    if (SAVE_GU) {
+                        G[o] = g;
+                        U[o] = u;
+                    }
+                    H[o] = __float2bfloat16(glu_silu(__bfloat162float(g)) *
+                                            __bfloat162float(u));
+                }
+            }
+        }
+    }
+}
+
+// dX[r] = dg[r] . Wg[e] + du[r] . Wu[e]: the dgrad K loop run twice, over
+// (dg, Wg) then (du, Wu), into ONE fp32 accumulator -- one launch and one
+// rounding instead of two dgrads and a bf16 add.
+template <int BN>
+__global__ __launch_bounds__(NTHREADS)
+void grouped_glu_dgrad_kernel(const bf16* __restrict__ dG,
+                              const bf16* __restrict__ dU,
+                              const WeightPtrs wg, const WeightPtrs wu,
+                              const int* __restrict__ offsets,
+                              bf16* __restrict__ dX, int T, int E, int I,
+                              int K, int n_tiles_n) {
+    constexpr int NF = BN / 32;  // 16-col fragments per wave
+    const int wgid = xcd_remap(blockIdx.x, gridDim.x);
+    const int mt = wgid / n_tiles_n;
+    const int tn = wgid % n_tiles_n;
+
+    const MTile t = locate_m_tile(offsets, mt, T, E);
+    const int e = t.e, row0 = t.row0, rows_valid = t.rows_valid;
+    if (e < 0) return;  // surplus block of the host's upper bound
+
+    __shared__ __attribute__((aligned(16))) bf16 a_t[2][BM * BK];
+    __shared__ __attribute__((aligned(16))) bf16 b_t[2][BK * BN];
+
+    const int tid = threadIdx.x;
+    const int wave = tid / WAVE_SIZE;
+    const int lane = tid % WAVE_SIZE;
+    const int lgrp = lane >> 4, lcol = lane & 15;
+    const int wr = wave >> 1, wn = wave & 1;  // 2x2 waves of 64 x BN/2
+
+    frag_cd acc[4][NF];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = frag_cd{0.f, 0.f, 0.f, 0.f};
+
+    const int64_t col0 = (int64_t)tn * BN;
+    const int n_kt = I / BK;  // steps per product
+    const bf16* ag = dG + (int64_t)row0 * I;
+    const bf16* au = dU + (int64_t)row0 * I;
+    const bf16* __restrict__ Wg = wg.w[e] + col0;
+    const bf16* __restrict__ Wu = wu.w[e] + col0;
+    auto stage = [&](int buf, int st) {  // step st of 2 * n_kt; uniform
+        const bool up = st >= n_kt;
+        const int64_t k0 = (int64_t)(up ? st - n_kt : st) * BK;
+        stage_tile<BM, BK, false>(a_t[buf], (up ? au : ag) + k0, I,
+                                  rows_valid - 1, wave, lane);
+        stage_tile<BK, BN, true>(b_t[buf], (up ? Wu : Wg) + k0 * K, K, BK - 1,
+                                 wave, lane);
+    };
+
+    stage(0, 0);
+    __syncthreads();  // drains the glds (vmcnt(0))
+
+    int buf = 0;
+    for (int st = 0; st < 2 * n_kt; ++st) {
+        if (st + 1 < 2 * n_kt) stage(buf ^ 1, st + 1);
+#pragma unroll
+        for (int kk = 0; kk < BK / 32; ++kk) {
+            frag_ab av[4];
+#pragma unroll
+            for (int mf = 0; mf < 4; ++mf) {
+                av[mf] = read_frag_row(a_t[buf], wr * 64 + mf * 16 + lcol,
+                                       kk * 4 + lgrp);
+            }
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf) {
+                const frag_ab bv = read_frag_tr<BN>(
+                    b_t[buf], kk * 32, wn * (BN / 2) + nf * 16, lgrp, lcol);
+#pragma unroll
+                for (int mf = 0; mf < 4; ++mf) {
+                    acc[mf][nf] = MFMA16(av[mf], bv, acc[mf][nf]);
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    bf16* c_base = dX + (int64_t)row0 * K;
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf) {
+        const int64_t col = col0 + wn * (BN / 2) + nf * 16 + lcol;
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = wr * 64 + mf * 16 + 4 * lgrp + r;
+                if (row < rows_valid) {
+                    c_base[(int64_t)row * K + col] = (bf16)acc[mf][nf][r];
                 }
             }
         }
@@ -590,4 +828,100 @@ std::vector<torch::Tensor> grouped_gemm_wgrad(torch::Tensor dY,
 #undef LAUNCH
     HIP_CHECK_LAUNCH();
     return {dW, db};
+}
+
+namespace {
+
+// Both tables of a gated bank: E matrices of one [I,K] shape each.
+void collect_glu_weights(const std::vector<torch::Tensor>& w_gate,
+                         const std::vector<torch::Tensor>& w_up,
+                         const torch::Tensor& like, WeightPtrs& wg,
+                         WeightPtrs& wu, int64_t& I, int64_t& K) {
+    int64_t Iu, Ku;
+    collect_weights(w_gate, like, wg, I, K);
+    collect_weights(w_up, like, wu, Iu, Ku);
+    TORCH_CHECK(w_gate.size() == w_up.size() && Iu == I && Ku == K,
+                "grouped_glu: gate and up banks must hold the same number "
+                "of [I,K] weights");
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> grouped_glu_fwd(torch::Tensor X,
+                                           std::vector<torch::Tensor> w_gate,
+                                           std::vector<torch::Tensor> w_up,
+                                           torch::Tensor offsets,
+                                           bool save_gu) {
+    check_rows(X, "X");
+    WeightPtrs wg, wu;
+    int64_t I, K;
+    collect_glu_weights(w_gate, w_up, X, wg, wu, I, K);
+    const int64_t E = (int64_t)w_gate.size(), T = X.size(0);
+    TORCH_CHECK(X.size(1) == K, "grouped_glu_fwd: X is [T,", X.size(1),
+                "] but weights are [", I, ",", K, "]");
+    check_offsets(offsets, X, E);
+    auto H = torch::empty({T, I}, X.options());
+    torch::Tensor G, U;
+    if (save_gu) {
+        G = torch::empty({T, I}, X.options());
+        U = torch::empty({T, I}, X.options());
+    } else {
+        G = torch::empty({0}, X.options());
+        U = torch::empty({0}, X.options());
+    }
+    if (T == 0) return {H, G, U};
+    const int64_t n_tiles_n = I / 64;
+    const int64_t grid = m_tiles_bound(T, E) * n_tiles_n;
+    TORCH_CHECK(grid < (int64_t)1 << 31, "grouped_glu_fwd: grid too large");
+    auto stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH(SAVEV)                                                         \
+    hipLaunchKernelGGL((grouped_glu_fwd_kernel<SAVEV>),                       \
+        dim3((unsigned)grid), dim3(NTHREADS), 0, stream,                      \
+        reinterpret_cast<const bf16*>(X.data_ptr()), wg, wu,                  \
+        offsets.data_ptr<int>(), reinterpret_cast<bf16*>(H.data_ptr()),       \
+        reinterpret_cast<bf16*>(G.data_ptr()),                                \
+        reinterpret_cast<bf16*>(U.data_ptr()), (int)T, (int)E, (int)K,        \
+        (int)I, (int)n_tiles_n)
+    if (save_gu) LAUNCH(true);
+    else LAUNCH(false);
+#undef LAUNCH
+    HIP_CHECK_LAUNCH();
+    return {H, G, U};
+}
+
+torch::Tensor grouped_glu_dgrad(torch::Tensor dG, torch::Tensor dU,
+                                std::vector<torch::Tensor> w_gate,
+                                std::vector<torch::Tensor> w_up,
+                                torch::Tensor offsets) {
+    check_rows(dG, "dg");
+    check_rows(dU, "du");
+    WeightPtrs wg, wu;
+    int64_t I, K;
+    collect_glu_weights(w_gate, w_up, dG, wg, wu, I, K);
+    const int64_t E = (int64_t)w_gate.size(), T = dG.size(0);
+    TORCH_CHECK(dU.device() == dG.device() && dG.size(1) == I &&
+                    dU.size(0) == T && dU.size(1) == I,
+                "grouped_glu_dgrad: dg and du must both be [T,", I,
+                "] on one device");
+    check_offsets(offsets, dG, E);
+    auto dX = torch::empty({T, K}, dG.options());
+    if (T == 0) return dX;
+    // output columns run over K, which is only a multiple of 64
+    const int bn = (K % 128 == 0) ? 128 : 64;
+    const int64_t n_tiles_n = K / bn;
+    const int64_t grid = m_tiles_bound(T, E) * n_tiles_n;
+    TORCH_CHECK(grid < (int64_t)1 << 31, "grouped_glu_dgrad: grid too large");
+    auto stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH(BNV)                                                           \
+    hipLaunchKernelGGL((grouped_glu_dgrad_kernel<BNV>),                       \
+        dim3((unsigned)grid), dim3(NTHREADS), 0, stream,                      \
+        reinterpret_cast<const bf16*>(dG.data_ptr()),                         \
+        reinterpret_cast<const bf16*>(dU.data_ptr()), wg, wu,                 \
+        offsets.data_ptr<int>(), reinterpret_cast<bf16*>(dX.data_ptr()),      \
+        (int)T, (int)E, (int)I, (int)K, (int)n_tiles_n)
+    if (bn == 128) LAUNCH(128);
+    else LAUNCH(64);
+#undef LAUNCH
+    HIP_CHECK_LAUNCH();
+    return dX;
 }
