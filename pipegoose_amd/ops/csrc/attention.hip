@@ -293,6 +293,7 @@ __device__ __forceinline__ float u2f(unsigned u) { return __uint_as_float(u); }
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
 using lds_bf16x4_p = __attribute__((address_space(3))) bf16x4*;
 
@@ -552,7 +553,9 @@ void attn_fwd_v2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                 mx = fmaxf(u2f(sw[0]), u2f(sw[1]));
             }
             const float m_new = fmaxf(m_run, mx);
-            const float alpha = exp2f(m_run - m_new);
+            // raw v_exp_f32 (arguments are <= 0; results below 2^-126 flush
+            // to zero, where exp2f's guarded expansion returned a denormal)
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             m_run = m_new;
             l_run *= alpha;
 #pragma unroll
@@ -565,7 +568,7 @@ void attn_fwd_v2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
             for (int ns = 0; ns < 2; ++ns) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float pv = exp2f(st[ns][r] - m_new);
+                    const float pv = __builtin_amdgcn_exp2f(st[ns][r] - m_new);
                     st[ns][r] = pv;
                     sr[ns * 16 + r] = pv;
                 }
@@ -1246,6 +1249,47 @@ void attn_bwd_dq_kernel(const bf16* __restrict__ dout,
 // row-major reads spread across banks).
 namespace {
 
+// The D=128 kernels sit at the register cap, and a second (mask-free) copy
+// of the sub-tile body makes them spill: they keep one body that applies the
+// mask as a select on every sub-tile (a no-op for fully visible launches).
+template <int D> constexpr bool peel_unmasked = (D == 64);
+
+// a*b + c*d with BOTH products rounded before the add. The dkdv kernels have
+// always formed the exponent this way; a contracted fma would move its
+// roundings, and with them bits of P, dS and every gradient.
+__device__ __forceinline__ float mul2_add(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    return a * b + c * d;
+}
+
+// two floats -> one packed bf16 pair (round-to-nearest-even): a vector
+// conversion, so that it compiles to ONE v_cvt_pk_bf16_f32 (converting the
+// halves one by one costs two of them plus a shift and an or per pair)
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    using f32x2 = __attribute__((ext_vector_type(2))) float;
+    using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+    const f32x2 f = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2));
+}
+
+// Half hf of a 32x32 C fragment (8 registers) as a B-fragment with the C
+// row axis as k: each lane holds rows 8g + 4*hi + 0..3 and needs 8
+// consecutive ones, so the half-waves exchange word pairs.
+__device__ __forceinline__ frag_ab c_to_bfrag(const f32x16& x, int hf) {
+    const uint32_t wa = pack_bf16x2(x[8 * hf + 0], x[8 * hf + 1]);
+    const uint32_t wc = pack_bf16x2(x[8 * hf + 2], x[8 * hf + 3]);
+    const uint32_t wb = pack_bf16x2(x[8 * hf + 4], x[8 * hf + 5]);
+    const uint32_t wd = pack_bf16x2(x[8 * hf + 6], x[8 * hf + 7]);
+    auto s1 = __builtin_amdgcn_permlane32_swap(wa, wb, false, false);
+    auto s2 = __builtin_amdgcn_permlane32_swap(wc, wd, false, false);
+    union { frag_ab f; uint32_t u[4]; } out;
+    out.u[0] = s1[0];
+    out.u[1] = s2[0];
+    out.u[2] = s1[1];
+    out.u[3] = s2[1];
+    return out.f;
+}
+
 // element index into a sub-tiled [R][D] image; DBLK = D/16
 template <int D>
 __device__ __forceinline__ int sub_idx(int row, int elem_col) {
@@ -1282,6 +1326,7 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
     constexpr int ROWS = WAVES * 32;
     constexpr int DCH = D / 16;
     constexpr int DSUB = D / 32;
+    constexpr bool PEEL = peel_unmasked<D>;
     constexpr int VST = (D / 16) * 64;
     constexpr int NPK = KVB * (D / 8);          // K single-row packets
     constexpr int KPL = (NPK + NT - 1) / NT;
@@ -1311,6 +1356,9 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
 
     const int qr0 = qblock * ROWS + wave * 32;
     const int iq = qr0 + l31;
+    // same value, but known wave-uniform to the compiler: the tile
+    // classification below then branches on scalars, not on EXEC
+    const int qr0_u = __builtin_amdgcn_readfirstlane(qr0);
 
     frag_ab bQ[DCH], bDO[DCH];
     {
@@ -1402,11 +1450,14 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
         const bool last = (nb + 1 == nkv);
         if (EARLY_LOAD && !last) stage_load(nb + 1);
 
-        const bool active = full_vis || (kvrow0 + kv_off <= qr0 + 31);
+        const bool active = full_vis || (kvrow0 + kv_off <= qr0_u + 31);
         if (active) {
             // D=128 must NOT unroll (doubled live f32x16 pairs spill);
-            // D=64 has register headroom and full unroll measured faster
-            auto ns_body = [&](int ns) {
+            // D=64 has register headroom and full unroll measured faster.
+            // MASKED is a compile-time tag: sub-tiles wholly at or below the
+            // wave's diagonal run the body without any mask instruction.
+            auto ns_body = [&](int ns, auto masked_t) {
+                constexpr bool MASKED = decltype(masked_t)::value;
                 frag_ab dsfrag[2];
                 f32x16 st, dp;
 #pragma unroll
@@ -1423,38 +1474,33 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
                     dp = MFMA_32x32x16(aV, bDO[c], dp);  // dP^T = V·dO^T
                 }
                 __builtin_amdgcn_s_setprio(0);
+                // softmax/dS phase. Register r is kv row jk = iq + dj + roff(r)
+                // with roff(r) = 8*(r>>2) + (r&3). Every value is rounded
+                // exactly where it always was (st*scale2, then one fma with
+                // the bias, then -lse2; dS scaled per element), so results
+                // are bitwise what the branchy form gave; only the work
+                // around them is gone. The position difference goes to float
+                // once per sub-tile: dj and roff are small integers, so
+                // fdj + roff is exact. The exponent is <= ~0 for live
+                // elements (lse is the row's log-sum), so the raw v_exp_f32
+                // serves: results below 2^-126 flush to zero and vanish in
+                // the bf16 rounding. Masked elements are selected away AFTER
+                // the exp (it may be +inf there), never multiplied.
+                const int dj = kvrow0 + ns * 32 + 4 * hi + kv_off - iq;
+                const float fdj = (float)dj;
+                const bool all_live = !PEEL && full_vis;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int jk = kvrow0 + ns * 32 + (r & 3) + 8 * (r >> 2) +
-                                   4 * hi + kv_off;
-                    const float z2 = st[r] * scale2 +
-                                     slope2 * (float)(jk - iq);
-                    const float p = (jk <= iq) ? exp2f(z2 - lse2) : 0.f;
+                    const int roff = (r & 3) + 8 * (r >> 2);
+                    const float z2 = fmaf(slope2, fdj + (float)roff,
+                                          st[r] * scale2);
+                    float p = __builtin_amdgcn_exp2f(z2 - lse2);
+                    if (MASKED) p = (all_live || dj + roff <= 0) ? p : 0.f;
                     st[r] = p * (dp[r] - dlt) * scale;  // dS^T
                 }
                 // pack dS^T into B-fragments (k = kv), as in the forward
 #pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    union { __bf16 h2[2]; uint32_t u; } wa, wb2, wc, wd;
-                    wa.h2[0] = (__bf16)st[8 * hf + 0];
-                    wa.h2[1] = (__bf16)st[8 * hf + 1];
-                    wc.h2[0] = (__bf16)st[8 * hf + 2];
-                    wc.h2[1] = (__bf16)st[8 * hf + 3];
-                    wb2.h2[0] = (__bf16)st[8 * hf + 4];
-                    wb2.h2[1] = (__bf16)st[8 * hf + 5];
-                    wd.h2[0] = (__bf16)st[8 * hf + 6];
-                    wd.h2[1] = (__bf16)st[8 * hf + 7];
-                    auto s1 = __builtin_amdgcn_permlane32_swap(wa.u, wb2.u,
-                                                              false, false);
-                    auto s2 = __builtin_amdgcn_permlane32_swap(wc.u, wd.u,
-                                                              false, false);
-                    union { frag_ab f; uint32_t u[4]; } out;
-                    out.u[0] = s1[0];
-                    out.u[1] = s2[0];
-                    out.u[2] = s1[1];
-                    out.u[3] = s2[1];
-                    dsfrag[hf] = out.f;
-                }
+                for (int hf = 0; hf < 2; ++hf) dsfrag[hf] = c_to_bfrag(st, hf);
                 // dQ^T += K^T·dS^T for this ns's two kv chunks (keeps the
                 // fragment set at 2 so D=128 stays under the VGPR cap)
 #pragma unroll
@@ -1477,12 +1523,21 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
                     __builtin_amdgcn_s_setprio(0);
                 }
             };
+            // wave-uniform classification of one 32x32 sub-tile: no kv row
+            // of it lies above the wave's first q row
+            auto ns_run = [&](int ns) {
+                if (PEEL &&
+                    (full_vis || kvrow0 + ns * 32 + 31 + kv_off <= qr0_u))
+                    ns_body(ns, std::false_type{});
+                else
+                    ns_body(ns, std::true_type{});
+            };
             if (D == 128) {
 #pragma unroll 1
-                for (int ns = 0; ns < 2; ++ns) ns_body(ns);
+                for (int ns = 0; ns < 2; ++ns) ns_run(ns);
             } else {
-                ns_body(0);
-                ns_body(1);
+                ns_run(0);
+                ns_run(1);
             }
         }
         if (!last) {
@@ -1532,12 +1587,14 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
     constexpr int DCH = D / 16;
     constexpr int DSUB = D / 32;
     constexpr int NP = QT * (D / 8);         // single-row staging packets
+    constexpr bool PEEL = peel_unmasked<D>;
     constexpr int PPL = (NP + NT - 1) / NT;
 
     __shared__ __attribute__((aligned(16))) bf16 qs_lds[2][QT * D];
     __shared__ __attribute__((aligned(16))) bf16 dos_lds[2][QT * D];
-    __shared__ float lse_lds[2][QT];
-    __shared__ float dlt_lds[2][QT];
+    // row statistics, 16-B aligned for the b128 reads of the softmax phase
+    __shared__ __attribute__((aligned(16))) float lse_lds[2][QT];
+    __shared__ __attribute__((aligned(16))) float dlt_lds[2][QT];
 
     const int nb = blockIdx.x;
     const int h = blockIdx.y;   // KV head
@@ -1551,6 +1608,9 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
 
     const int kv0w = nb * ROWS + wave * 32;  // wave's kv rows
     const int n_glob = kv0w + l31;
+    // same value, but known wave-uniform to the compiler (scalar branches
+    // for the tile skip and the masked/unmasked classification)
+    const int kv0w_u = __builtin_amdgcn_readfirstlane(kv0w);
     const float LOG2E = 1.4426950408889634f;
     const float scale2 = scale * LOG2E;
 
@@ -1639,9 +1699,12 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
             if (EARLY && !last) stage_load(q0 + QT);
 
             // wave-skip: a q-tile entirely above this wave's diagonal
-            const bool active = full_vis || (q0 + QT - 1 >= kv0w + kv_off);
+            const bool active = full_vis || (q0 + QT - 1 >= kv0w_u + kv_off);
             if (active) {
-                auto qs_body = [&](int qs2c) {
+                // MASKED is a compile-time tag: sub-tiles wholly at or below
+                // the wave's diagonal run the body without mask instructions
+                auto qs_body = [&](int qs2c, auto masked_t) {
+                    constexpr bool MASKED = decltype(masked_t)::value;
                     f32x16 st, dp;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
@@ -1661,83 +1724,54 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
                         }
                     }
                     __builtin_amdgcn_s_setprio(0);
-                    const int jk = n_glob + kv_off;
+                    // softmax/dS phase. Register r is q row iq with
+                    // jk - iq = dji - roff(r), roff(r) = 8*(r>>2) + (r&3).
+                    // Every value is rounded exactly where it always was
+                    // (st*scale2 and slope2*(jk-iq) each rounded, added, then
+                    // -lse; dS scaled per element), so results are bitwise
+                    // what the branchy form gave; only the work around them
+                    // is gone. The position difference goes to float once
+                    // per sub-tile: both are small integers, so fdji - roff
+                    // is exact. The exponent is <= ~0 for live elements (lse
+                    // is the row's log-sum), so the raw v_exp_f32 serves:
+                    // results below 2^-126 flush to zero and vanish in P's
+                    // bf16 rounding. Masked elements are selected away AFTER
+                    // the exp (it may be +inf there), never multiplied.
+                    const int dji = n_glob + kv_off - q0 - qs2c * 32 - 4 * hi;
+                    const float fdji = (float)dji;
+                    const bool all_live = !PEEL && full_vis;
+                    // Row statistics: register r is q row 8*(r>>2) + (r&3)
+                    // + 4*hi, so each group of four registers reads four
+                    // consecutive floats with one ds_read_b128 (the scheduler
+                    // moves the reads up as far as registers allow).
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int q_loc = qs2c * 32 + (r & 3) + 8 * (r >> 2) +
-                                          4 * hi;
-                        const int iq = q0 + q_loc;
-                        const float z2 = st[r] * scale2 +
-                                         slope2 * (float)(jk - iq);
-                        const float p = (jk <= iq)
-                            ? exp2f(z2 - lse_lds[cur][q_loc]) : 0.f;
-                        st[r] = p;                                   // P
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 l4 = *reinterpret_cast<const f32x4*>(
+                            &lse_lds[cur][qs2c * 32 + 8 * g + 4 * hi]);
+                        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
                         if (DO_DK)
-                            dp[r] = p * (dp[r] - dlt_lds[cur][q_loc]) * scale;
+                            d4 = *reinterpret_cast<const f32x4*>(
+                                &dlt_lds[cur][qs2c * 32 + 8 * g + 4 * hi]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int r = 4 * g + e;
+                            const int roff = e + 8 * g;
+                            const float z2 = mul2_add(
+                                st[r], scale2, slope2, fdji - (float)roff);
+                            float p = __builtin_amdgcn_exp2f(z2 - l4[e]);
+                            if (MASKED)
+                                p = (all_live || dji <= roff) ? p : 0.f;
+                            st[r] = p;                               // P
+                            if (DO_DK)
+                                dp[r] = p * (dp[r] - d4[e]) * scale; // dS
+                        }
                     }
                     // pack P and dS into B-fragments over the q axis
                     frag_ab pfrag[2], dsfrag[2];
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
-                        union { __bf16 h2[2]; uint32_t u; } wa, wb2, wc, wd;
-                        if (!DO_DV) {
-                            wa.h2[0] = (__bf16)dp[8 * hf + 0];
-                            wa.h2[1] = (__bf16)dp[8 * hf + 1];
-                            wc.h2[0] = (__bf16)dp[8 * hf + 2];
-                            wc.h2[1] = (__bf16)dp[8 * hf + 3];
-                            wb2.h2[0] = (__bf16)dp[8 * hf + 4];
-                            wb2.h2[1] = (__bf16)dp[8 * hf + 5];
-                            wd.h2[0] = (__bf16)dp[8 * hf + 6];
-                            wd.h2[1] = (__bf16)dp[8 * hf + 7];
-                            auto t1 = __builtin_amdgcn_permlane32_swap(
-                                wa.u, wb2.u, false, false);
-                            auto t2 = __builtin_amdgcn_permlane32_swap(
-                                wc.u, wd.u, false, false);
-                            union { frag_ab f; uint32_t u[4]; } o2;
-                            o2.u[0] = t1[0];
-                            o2.u[1] = t2[0];
-                            o2.u[2] = t1[1];
-                            o2.u[3] = t2[1];
-                            dsfrag[hf] = o2.f;
-                            continue;
-                        }
-                        wa.h2[0] = (__bf16)st[8 * hf + 0];
-                        wa.h2[1] = (__bf16)st[8 * hf + 1];
-                        wc.h2[0] = (__bf16)st[8 * hf + 2];
-                        wc.h2[1] = (__bf16)st[8 * hf + 3];
-                        wb2.h2[0] = (__bf16)st[8 * hf + 4];
-                        wb2.h2[1] = (__bf16)st[8 * hf + 5];
-                        wd.h2[0] = (__bf16)st[8 * hf + 6];
-                        wd.h2[1] = (__bf16)st[8 * hf + 7];
-                        auto s1 = __builtin_amdgcn_permlane32_swap(
-                            wa.u, wb2.u, false, false);
-                        auto s2 = __builtin_amdgcn_permlane32_swap(
-                            wc.u, wd.u, false, false);
-                        union { frag_ab f; uint32_t u[4]; } out;
-                        out.u[0] = s1[0];
-                        out.u[1] = s2[0];
-                        out.u[2] = s1[1];
-                        out.u[3] = s2[1];
-                        pfrag[hf] = out.f;
-                        if (!DO_DK) continue;
-
-                        wa.h2[0] = (__bf16)dp[8 * hf + 0];
-                        wa.h2[1] = (__bf16)dp[8 * hf + 1];
-                        wc.h2[0] = (__bf16)dp[8 * hf + 2];
-                        wc.h2[1] = (__bf16)dp[8 * hf + 3];
-                        wb2.h2[0] = (__bf16)dp[8 * hf + 4];
-                        wb2.h2[1] = (__bf16)dp[8 * hf + 5];
-                        wd.h2[0] = (__bf16)dp[8 * hf + 6];
-                        wd.h2[1] = (__bf16)dp[8 * hf + 7];
-                        s1 = __builtin_amdgcn_permlane32_swap(
-                            wa.u, wb2.u, false, false);
-                        s2 = __builtin_amdgcn_permlane32_swap(
-                            wc.u, wd.u, false, false);
-                        out.u[0] = s1[0];
-                        out.u[1] = s2[0];
-                        out.u[2] = s1[1];
-                        out.u[3] = s2[1];
-                        dsfrag[hf] = out.f;
+                        if (DO_DV) pfrag[hf] = c_to_bfrag(st, hf);
+                        if (DO_DK) dsfrag[hf] = c_to_bfrag(dp, hf);
                     }
                     // dV^T += dO^T·P  and  dK^T += Q^T·dS (transpose reads)
 #pragma unroll
@@ -1775,12 +1809,24 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
                         __builtin_amdgcn_s_setprio(0);
                     }
                 };
-                if (D == 128) {
+                // wave-uniform classification of one 32x32 sub-tile: none
+                // of the wave's kv rows lies above the sub-tile's first q row
+                auto qs_run = [&](int qs2c) {
+                    if (PEEL &&
+                        (full_vis || kv0w_u + 31 + kv_off <= q0 + qs2c * 32))
+                        qs_body(qs2c, std::false_type{});
+                    else
+                        qs_body(qs2c, std::true_type{});
+                };
+                // rolled at D=128 (register cap) and in the 8-wave D=64 build,
+                // where four unrolled bodies (2 sub-tiles x masked/mask-free)
+                // spill 68 B
+                if (D == 128 || WAVES == 8) {
 #pragma unroll 1
-                    for (int qs2c = 0; qs2c < 2; ++qs2c) qs_body(qs2c);
+                    for (int qs2c = 0; qs2c < 2; ++qs2c) qs_run(qs2c);
                 } else {
-                    qs_body(0);
-                    qs_body(1);
+                    qs_run(0);
+                    qs_run(1);
                 }
             }
             if (!last) {
