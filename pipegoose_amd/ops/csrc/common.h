@@ -57,6 +57,35 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* smem) {
     return v;
 }
 
+// Two block-level sums for the price of one: same barriers as
+// block_reduce_sum.  `smem` needs 2 * blockDim.x/WAVE_SIZE floats.
+__device__ __forceinline__ void block_reduce_sum2(float& a, float& b, float* smem) {
+    const int lane = threadIdx.x & (WAVE_SIZE - 1);
+    const int wave = threadIdx.x / WAVE_SIZE;
+    const int n_waves = blockDim.x / WAVE_SIZE;
+    a = wave_reduce_sum(a);
+    b = wave_reduce_sum(b);
+    if (lane == 0) {
+        smem[wave] = a;
+        smem[n_waves + wave] = b;
+    }
+    __syncthreads();
+    a = (threadIdx.x < n_waves) ? smem[threadIdx.x] : 0.0f;
+    b = (threadIdx.x < n_waves) ? smem[n_waves + threadIdx.x] : 0.0f;
+    if (wave == 0) {
+        a = wave_reduce_sum(a);
+        b = wave_reduce_sum(b);
+        if (lane == 0) {
+            smem[0] = a;
+            smem[n_waves] = b;
+        }
+    }
+    __syncthreads();
+    a = smem[0];
+    b = smem[n_waves];
+    __syncthreads();
+}
+
 __device__ __forceinline__ float block_reduce_max(float v, float* smem) {
     const int lane = threadIdx.x & (WAVE_SIZE - 1);
     const int wave = threadIdx.x / WAVE_SIZE;

@@ -34,6 +34,9 @@ __global__ void ce_fwd_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float f = to_float(pkt.v[j]);
+            // a -inf (masked) logit adds nothing; while m is still -inf,
+            // exp(f - m) would be exp(NaN)
+            if (f == -INFINITY) continue;
             if (f > m) {
                 s *= __expf(m - f);
                 m = f;
@@ -43,6 +46,7 @@ __global__ void ce_fwd_kernel(
     }
     for (int i = VV * 8 + threadIdx.x; i < V; i += BLOCK) {
         float f = to_float(xr[i]);
+        if (f == -INFINITY) continue;
         if (f > m) {
             s *= __expf(m - f);
             m = f;

@@ -19,7 +19,7 @@ __global__ void layer_norm_fwd_kernel(
     const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
     T* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
     int H, float eps) {
-    __shared__ float smem[BLOCK / WAVE_SIZE];
+    __shared__ float smem[2 * BLOCK / WAVE_SIZE];
     const int64_t row = blockIdx.x;
     const T* xr = x + row * (int64_t)H;
     T* yr = y + row * (int64_t)H;
@@ -51,8 +51,36 @@ __global__ void layer_norm_fwd_kernel(
     sum = block_reduce_sum(sum, smem);
     sumsq = block_reduce_sum(sumsq, smem);
 
-    const float mean = sum / H;
-    const float var = sumsq / H - mean * mean;
+    float mean = sum / H;
+    float var = sumsq / H - mean * mean;
+    // E[x^2] - mean^2 is good to a few ulp of var while |mean| <= std.  Past
+    // that it cancels (rstd 6% off at mean 1000, var < 0 -> NaN on
+    // near-constant rows), so such a row takes a second pass over the cached
+    // registers (or the re-read row): var from the deviations d = x - mean,
+    // which are then nearly exact, and sum(d)/H, which takes the rounding of
+    // the 256-way fp32 row sum out of the mean.  The test is the same for
+    // the whole block, and a garbled var only ever errs towards the pass.
+    if (mean * mean > var) {
+        float sd = 0.f, sq = 0.f;
+        for (int i = threadIdx.x, c = 0; i < HV; i += BLOCK, ++c) {
+            V pkt = cached ? reg[c] : reinterpret_cast<const V*>(xr)[i];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float d = to_float(pkt.v[j]) - mean;
+                sd += d;
+                sq += d * d;
+            }
+        }
+        for (int i = HV * 8 + threadIdx.x; i < H; i += BLOCK) {
+            float d = to_float(xr[i]) - mean;
+            sd += d;
+            sq += d * d;
+        }
+        block_reduce_sum2(sd, sq, smem);
+        const float dm = sd / H;
+        var = fmaxf(sq / H - dm * dm, 0.f);
+        mean += dm;
+    }
     const float rstd = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
         mean_out[row] = mean;
@@ -360,7 +388,7 @@ __global__ void layer_norm_res_fwd_kernel(
     T* __restrict__ s, T* __restrict__ y,
     float* __restrict__ mean_out, float* __restrict__ rstd_out,
     int H, float eps) {
-    __shared__ float smem[BLOCK / WAVE_SIZE];
+    __shared__ float smem[2 * BLOCK / WAVE_SIZE];
     const int64_t row = blockIdx.x;
     const T* xr = x + row * (int64_t)H;
     const T* rr = r + row * (int64_t)H;
@@ -401,8 +429,31 @@ __global__ void layer_norm_res_fwd_kernel(
     sum = block_reduce_sum(sum, smem);
     sumsq = block_reduce_sum(sumsq, smem);
 
-    const float mean = sum / H;
-    const float var = sumsq / H - mean * mean;
+    float mean = sum / H;
+    float var = sumsq / H - mean * mean;
+    // |mean| > std: second pass over the rounded s (registers, or this
+    // thread's own stores read back), see layer_norm_fwd_kernel
+    if (mean * mean > var) {
+        float sd = 0.f, sq = 0.f;
+        for (int i = threadIdx.x, c = 0; i < HV; i += BLOCK, ++c) {
+            V ps = cached ? reg[c] : reinterpret_cast<const V*>(sr)[i];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float d = to_float(ps.v[j]) - mean;
+                sd += d;
+                sq += d * d;
+            }
+        }
+        for (int i = HV * 8 + threadIdx.x; i < H; i += BLOCK) {
+            float d = to_float(sr[i]) - mean;
+            sd += d;
+            sq += d * d;
+        }
+        block_reduce_sum2(sd, sq, smem);
+        const float dm = sd / H;
+        var = fmaxf(sq / H - dm * dm, 0.f);
+        mean += dm;
+    }
     const float rstd = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
         mean_out[row] = mean;

@@ -1,7 +1,9 @@
-"""Fused LayerNorm: one-pass mean/var with 64-wide wave reductions on gfx950.
+"""Fused LayerNorm: one-pass mean/var with 64-wide wave reductions on gfx950,
+and a second pass over the cached row where |mean| > std.
 
-CPU path: torch.nn.functional.layer_norm (the numerics oracle the GPU kernel
-is tested against, tests/ops/test_layer_norm.py).
+CPU path: torch.nn.functional.layer_norm (the GPU kernel is tested against it
+and an fp64 reference in tests/ops/test_kernels_gpu.py and
+tests/ops/test_rowwise_edges_gpu.py).
 
 MI355X-native kernel wrapper, no reference counterpart (the reference used
 plain nn.LayerNorm — nn/tensor_parallel/layer_norm.py:23-25).
