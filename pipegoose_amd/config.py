@@ -13,8 +13,10 @@ Usage::
     cfg = RuntimeConfig.from_yaml("job.yaml")   # explicit file
     cfg.apply_env()                     # export back as PG_* for kernels
 
-The HIP extension reads its knobs via getenv at first use, so apply_env()
-must run before the first kernel launch to take effect there.
+The HIP extension reads its one knob (PG_BGELU_ROWS) via getenv at first use,
+so apply_env() must run before the first kernel launch to take effect there.
+Attention has no switches: its kernel choice is a fixed table of (S, D)
+(ext.attn_variant).
 """
 import dataclasses
 import os
@@ -23,9 +25,6 @@ from typing import Optional
 
 _ENV_MAP = {
     "bucket_size_mb": "PG_BUCKET_MB",
-    "attn_v2": "PG_ATTN_V2",
-    "attn_bwd_v2": "PG_ATTN_BWD_V2",
-    "attn_w4": "PG_ATTN_W4",
     "moe_grouped": "PG_MOE_GROUPED",
     "hand_gemm": "PG_HAND_GEMM",
     "bgelu_rows": "PG_BGELU_ROWS",
@@ -42,11 +41,11 @@ _ENV_MAP = {
 class RuntimeConfig:
     # communication
     bucket_size_mb: int = 25          # DP/ZeRO grad bucket size (xGMI-tuned)
-    # kernel variant switches (read by the HIP extension via getenv)
-    attn_v2: int = 1                  # 0 forces the v1 forward
-    attn_bwd_v2: int = 1              # 0 forces the v1 backward
-    attn_w4: int = 0                  # 1 forces 4-wave attention WGs (A/B)
-    moe_grouped: int = 0              # 1 = padded bmm bank, 2 = HIP grouped GEMM
+    # kernel variant switches
+    # MoE expert bank (experts.py): 0 = per-expert loop, 1 = padded bmm bank,
+    # 2 = HIP grouped-GEMM kernels, 3 = those plus the sync-free routing-plan/
+    # permute/combine kernels (mode 2 wherever the fused path does not apply)
+    moe_grouped: int = 0
     hand_gemm: int = 0                # 1 forces the hand MFMA GEMM
     bgelu_rows: int = 1024            # bias-gelu bwd grid rows
     disable_ext: int = 0              # 1 disables the HIP extension

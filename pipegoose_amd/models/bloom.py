@@ -175,9 +175,9 @@ class BloomAttention(nn.Module):
         if use_cache and present is None:
             present = (k, v)
 
-        from pipegoose_amd.ops.attention import (_kernel_supported,
-                                                 alibi_attention,
-                                                 alibi_attention_qkv)
+        from pipegoose_amd.ops.attention import (alibi_attention,
+                                                 alibi_attention_qkv,
+                                                 kernel_supported)
         if present is not None and getattr(present, "graph_mode", False):
             # hipGraph-capturable decode: constant shapes (full cache
             # length), position enters as DATA via the cache's device pos_t
@@ -201,7 +201,7 @@ class BloomAttention(nn.Module):
                 self.alibi_slopes.to(q.device, torch.float32), self.inv_norm,
                 parallel_context=self.parallel_context,
                 parallel_mode=ParallelMode.CONTEXT).to(q.dtype)
-        elif past_kv is None and not use_cache and _kernel_supported(q):
+        elif past_kv is None and not use_cache and kernel_supported(q):
             # training fast path: backward writes one d(fused) buffer
             out = alibi_attention_qkv(fused, self.alibi_slopes, self.inv_norm)
         else:

@@ -147,9 +147,9 @@ class LlamaAttention(nn.Module):
         if use_cache and present is None:
             present = (k, v)
 
-        from pipegoose_amd.ops.attention import (_kernel_supported,
-                                                 alibi_attention)
-        kernel_ok = (_kernel_supported(q) and past_kv is None
+        from pipegoose_amd.ops.attention import (alibi_attention,
+                                                 kernel_supported)
+        kernel_ok = (kernel_supported(q) and past_kv is None
                      and not use_cache)
         if self._cp_size() > 1 and past_kv is None and not use_cache:
             from pipegoose_amd.nn.ring_attention import ring_attention_rotate

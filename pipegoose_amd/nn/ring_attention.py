@@ -24,6 +24,7 @@ from pipegoose_amd.distributed.parallel_context import ParallelContext
 from pipegoose_amd.distributed.parallel_mode import ParallelMode
 from pipegoose_amd.nn.tensor_parallel._functional import all_gather_sequence
 from pipegoose_amd.ops import get_extension
+from pipegoose_amd.ops.attention import kernel_supported
 
 
 def _block_attention_ref(q, k, v, slopes, scale, kv_off):
@@ -65,10 +66,7 @@ class _BlockAttn(torch.autograd.Function):
 
 
 def _block_attention(q, k, v, slopes, scale, kv_off):
-    use_kernel = (q.is_cuda and q.dtype == torch.bfloat16
-                  and q.size(-1) in (64, 128) and q.size(-2) % 64 == 0
-                  and get_extension() is not None)
-    if use_kernel:
+    if kernel_supported(q):
         return _BlockAttn.apply(q.contiguous(), k.contiguous(),
                                 v.contiguous(),
                                 slopes.to(q.device, torch.float32),
@@ -172,9 +170,7 @@ class _RingAttentionRotate(torch.autograd.Function):
         S_local = q.size(2)
         do = do.contiguous()
 
-        use_kernel = (q.is_cuda and q.dtype == torch.bfloat16
-                      and q.size(-1) in (64, 128) and S_local % 64 == 0
-                      and get_extension() is not None)
+        use_kernel = kernel_supported(q)   # q is this rank's local block
         dq = torch.zeros_like(q, dtype=torch.float32)
         cur_k, cur_v = k, v
         dk_acc = torch.zeros_like(k, dtype=torch.float32)

@@ -9,30 +9,30 @@ CPU path: sdpa math with the mask (numerics oracle).
 No reference counterpart (the reference has no attention kernels at all);
 this is MI355X-native.
 """
-import os
-
 import torch
 import torch.nn.functional as TF
 
 from pipegoose_amd.ops import get_extension
 
 
-def _kernel_supported(q: torch.Tensor) -> bool:
-    if not q.is_cuda or os.environ.get("PIPEGOOSE_DISABLE_EXT") == "1":
+def kernel_supported(q: torch.Tensor) -> bool:
+    """Whether the HIP attention kernels take q ([..., S, D], the block that
+    is actually handed to them): bf16 on the GPU, extension present, D in
+    {64, 128}, S a multiple of 64.  The one place that says so; the kernels'
+    own host checks raise on anything else."""
+    if not q.is_cuda or q.dtype != torch.bfloat16:
         return False
-    D = q.size(-1)
-    S = q.size(-2)
-    ext = get_extension()
-    if ext is None or not hasattr(ext, "attn_fwd"):
+    if get_extension() is None:   # not built, or PIPEGOOSE_DISABLE_EXT=1
         return False
-    return D in (64, 128) and S % 64 == 0 and q.dtype == torch.bfloat16
+    return q.size(-1) in (64, 128) and q.size(-2) % 64 == 0
+
+
+_kernel_supported = kernel_supported
 
 
 def _d_contig(t: torch.Tensor) -> torch.Tensor:
     # kernels take arbitrary [B,H,S,D] strides as long as d is contiguous —
     # the model's transposed views qualify, so no copies happen here
-    if os.environ.get("PG_ATTN_CONTIG") == "1":
-        return t.contiguous()
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
@@ -90,7 +90,7 @@ class _AlibiFlashAttentionFused(torch.autograd.Function):
 def alibi_attention_qkv(fused, slopes, scale):
     """fused: [B, S, H_local, 3, head_dim] straight from the QKV projection.
     Returns o with logical shape [B, H, S, hd] (physically [B, S, H, hd]).
-    Caller must have checked _kernel_supported on the q view."""
+    Caller must have checked kernel_supported on the q view."""
     return _AlibiFlashAttentionFused.apply(
         fused, slopes.to(device=fused.device, dtype=torch.float32), scale)
 
@@ -98,7 +98,7 @@ def alibi_attention_qkv(fused, slopes, scale):
 def alibi_attention(q, k, v, slopes, scale, mask_fallback=None):
     """q,k,v: [B, H, S, D] (any strides, d contiguous); slopes: [H] fp32;
     causal + alibi bias computed in-kernel."""
-    if _kernel_supported(q):
+    if kernel_supported(q):
         return _AlibiFlashAttention.apply(
             _d_contig(q), _d_contig(k), _d_contig(v),
             slopes.to(device=q.device, dtype=torch.float32), scale)

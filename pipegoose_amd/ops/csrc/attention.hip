@@ -1,42 +1,56 @@
 // Flash attention (causal + ALiBi) for gfx950 — hand-written CDNA4 MFMA.
 //
-// Replaces the sdpa-with-bias fallback: the ALiBi bias slope*(j-i) is
-// computed IN-KERNEL from per-head slopes, so no [H,S,S] bias tensor is
-// materialized or re-read from HBM (that tensor dominated the sdpa path's
-// memory traffic).  Online-softmax (flash2) with fp32 running stats.
+// The ALiBi bias slope*(j-i) and the causal mask are computed IN-KERNEL from
+// per-head slopes, so no [H,S,S] bias tensor is materialized or re-read from
+// HBM (that tensor dominated the sdpa-with-bias path's memory traffic).
+// Online softmax (flash2) with fp32 running stats; the backward is two-pass
+// (kv-outer dK/dV, q-outer dQ, plus a tiny delta = rowsum(dO*O) kernel),
+// recomputes P from (q, k, lse) and uses no atomics.  Tensors are [B,H,S,D]
+// logical with arbitrary strides (d contiguous); kv_off shifts the kv
+// positions (ring-attention blocks): <= -S = fully visible, 0 = causal.
 //
-// Tiling: one workgroup = 4 waves = 256 threads handles a 64-row Q block;
-// each wave owns 16 q rows.  K/V tiles (64 rows) stage through LDS; V is
-// stored transposed so the P·V MFMA's B-fragment reads are contiguous 16B.
-// MFMA: v_mfma_f32_16x16x32_bf16 (A/B: 8 bf16/lane; C/D: 4 fp32/lane,
-// row=(lane>>4)*4+reg, col=lane&15 — guide §3 fragment layout).
+// Two kernel families; select_variant() in the host section at the end of
+// this file (bound as attn_variant) is the one place that picks, for the
+// forward and the backward alike (D in {64,128}, S % 64 == 0):
+//
+//   S % 128 == 64  v1, 4 waves   fwd grid S/64;  bwd: delta, dkdv, dq
+//   S % 256 == 128 v2, 4 waves   fwd grid S/128; bwd: delta, dq_v2, dkdv_v2
+//   S % 256 == 0   v2, 8 waves   fwd grid S/256; bwd: delta, dq_v2, dkdv_v2
+//
+// v2 is the design (every shape the models and the benchmark use):
+// v_mfma_f32_32x32x16_bf16, a wave owns 32 rows, "swapped" products
+// (St = K·Q^T, O^T = V^T·P^T) so that a lane owns one q row and softmax
+// statistics are lane-local, XOR-swizzled and sub-tiled LDS images read with
+// ds_read_b64_tr_b16, double-buffered tiles, exp2 domain.  dkdv_v2 is one
+// fused kernel at D=64; at D=128 it would spill and runs as a dv-only pass
+// plus two half-width dk passes.
+//
+// v1 is the fallback for S % 128 == 64, which v2's 128-row workgroups cannot
+// tile: v_mfma_f32_16x16x32_bf16, one workgroup = 4 waves x 16 rows = 64 q
+// (or kv) rows, padded LDS rows, P bounced through LDS from C- to A-layout,
+// 16-lane shuffle reductions for the row statistics.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-#include "common.h"
+#include <string>
+#include <tuple>
+#include <type_traits>
 
+#include "mfma_frag.h"
+
+// ======================================================================
+// v1 forward: 4 waves x 16 q rows.  K/V tiles (64 rows) stage through LDS; V
+// is stored transposed so the P·V MFMA's B-fragment reads are contiguous 16B.
 namespace {
 
-using bf16 = __hip_bfloat16;
-using frag_ab = __attribute__((ext_vector_type(8))) __bf16;   // 8 bf16 = 4 VGPR
-using frag_cd = __attribute__((ext_vector_type(4))) float;    // 4 fp32
-
-__device__ __forceinline__ frag_cd MFMA_16x16x32(frag_ab a, frag_ab b, frag_cd c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-constexpr int BLOCK_M = 64;   // q rows per workgroup
+constexpr int BLOCK_M = 64;   // v1: q (or kv) rows per workgroup
 constexpr int BLOCK_N = 64;   // kv rows per LDS tile
-constexpr int NWAVES = 4;     // BLOCK_M / 16
+constexpr int NWAVES = 4;     // v1: BLOCK_M / 16
 constexpr int PAD = 8;        // bf16 elements (16 B) of row padding in LDS
 constexpr float NEG_INF = -1e30f;
 
-// A-fragment (M=16 side): row = lane&15, k = 8*(lane>>4) + i
-// B-fragment (N=16 side): col = lane&15, k = 8*(lane>>4) + i
-// C/D:                    col = lane&15, row = 4*(lane>>4) + reg
-
-template <int D, int MT, int WAVES = NWAVES>
-__global__ __launch_bounds__(WAVES * WAVE_SIZE)
+template <int D>
+__global__ __launch_bounds__(NWAVES * WAVE_SIZE)
 void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                      const bf16* __restrict__ v,
                      const float* __restrict__ slopes, float scale,
@@ -49,19 +63,15 @@ void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
     // Tensors are [B, H, S, D] LOGICAL with arbitrary strides (d contiguous):
     // the model's qkv views come straight from the fused projection with no
     // .contiguous() copies (those copies were ~6% of the training step).
-    // MT = q row-tiles per wave (16 rows each).  MT=2 doubles the MFMA work
-    // per LDS B-fragment read — the K/V tiles are read once per wave and
-    // used for 32 q rows.
     constexpr int DCH = D / 32;    // K-chunks per QK^T mfma row
     constexpr int DSUB = D / 16;   // output d-subtiles
     constexpr int KSTRIDE = D + PAD;
     constexpr int VSTRIDE = BLOCK_N + PAD;
-    constexpr int ROWS_PER_WG = WAVES * MT * 16;
-    constexpr int NT = WAVES * WAVE_SIZE;
+    constexpr int NT = NWAVES * WAVE_SIZE;
 
     __shared__ bf16 k_lds[BLOCK_N * KSTRIDE];
     __shared__ bf16 vt_lds[D * VSTRIDE];
-    __shared__ bf16 p_lds[WAVES][MT * 16 * VSTRIDE];
+    __shared__ bf16 p_lds[NWAVES][16 * VSTRIDE];
 
     const int qblock = blockIdx.x;
     const int h = blockIdx.y;
@@ -79,34 +89,30 @@ void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* vp = v + b * vb + hk * vh;
     bf16* op = o + b * ob + h * oh;
 
-    // wave owns rows [qrow0, qrow0 + MT*16)
-    const int qrow0 = qblock * ROWS_PER_WG + wave * (MT * 16);
+    // wave owns rows [qrow0, qrow0 + 16)
+    const int qrow0 = qblock * BLOCK_M + wave * 16;
     const float slope = slopes[h];
 
-    frag_ab aQ[MT][DCH];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const bf16* qrow = qp + (int64_t)(qrow0 + mt * 16 + lcol) * qs;
+    frag_ab aQ[DCH];
+    {
+        const bf16* qrow = qp + (int64_t)(qrow0 + lcol) * qs;
 #pragma unroll
         for (int c = 0; c < DCH; ++c) {
-            aQ[mt][c] = *reinterpret_cast<const frag_ab*>(qrow + c * 32 + 8 * lgrp);
+            aQ[c] = *reinterpret_cast<const frag_ab*>(qrow + c * 32 + 8 * lgrp);
         }
     }
 
-    frag_cd accO[MT][DSUB];
-    float m_run[MT][4], l_run[MT][4];
+    frag_cd accO[DSUB];
+    float m_run[4], l_run[4];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
+    for (int s = 0; s < DSUB; ++s) accO[s] = frag_cd{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < DSUB; ++s) accO[mt][s] = frag_cd{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { m_run[mt][r] = NEG_INF; l_run[mt][r] = 0.f; }
-    }
+    for (int r = 0; r < 4; ++r) { m_run[r] = NEG_INF; l_run[r] = 0.f; }
 
     // kv positions are globally shifted by kv_off (ring attention blocks):
     // kv_off <= -S means every kv position is visible (no causal cut)
     int n_kv_blocks = (kv_off <= -S) ? (S / BLOCK_N)
-        : (qblock * ROWS_PER_WG + ROWS_PER_WG - kv_off + BLOCK_N - 1) / BLOCK_N;
+        : (qblock * BLOCK_M + BLOCK_M - kv_off + BLOCK_N - 1) / BLOCK_N;
     n_kv_blocks = min(max(n_kv_blocks, 0), S / BLOCK_N);
     for (int nb = 0; nb < n_kv_blocks; ++nb) {
         const int kvrow0 = nb * BLOCK_N;
@@ -141,141 +147,111 @@ void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
         }
         __syncthreads();
 
+        // S = Q K^T for this wave's rows (16 x 64)
+        float s_tile[4][4];  // [nsub][reg]
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            // S = Q K^T for this row-tile (16 x 64)
-            float s_tile[4][4];  // [nsub][reg]
+        for (int ns = 0; ns < 4; ++ns) {
+            frag_cd acc = frag_cd{0.f, 0.f, 0.f, 0.f};
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int ns = 0; ns < 4; ++ns) {
-                frag_cd acc = frag_cd{0.f, 0.f, 0.f, 0.f};
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int c = 0; c < DCH; ++c) {
-                    frag_ab bK = *reinterpret_cast<const frag_ab*>(
-                        &k_lds[(ns * 16 + lcol) * KSTRIDE + c * 32 + 8 * lgrp]);
-                    acc = MFMA_16x16x32(aQ[mt][c], bK, acc);
-                }
-                __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int iq = qrow0 + mt * 16 + 4 * lgrp + r;
-                    const int jk = kvrow0 + ns * 16 + lcol + kv_off;
-                    float sv = acc[r] * scale + slope * (float)(jk - iq);
-                    s_tile[ns][r] = (jk <= iq) ? sv : NEG_INF;
-                }
+            for (int c = 0; c < DCH; ++c) {
+                frag_ab bK = *reinterpret_cast<const frag_ab*>(
+                    &k_lds[(ns * 16 + lcol) * KSTRIDE + c * 32 + 8 * lgrp]);
+                acc = MFMA_16x16x32(aQ[c], bK, acc);
             }
+            __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int iq = qrow0 + 4 * lgrp + r;
+                const int jk = kvrow0 + ns * 16 + lcol + kv_off;
+                float sv = acc[r] * scale + slope * (float)(jk - iq);
+                s_tile[ns][r] = (jk <= iq) ? sv : NEG_INF;
+            }
+        }
 
-            // online softmax update
-            float m_new[4];
+        // online softmax update
+        float m_new[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float mx = fmaxf(fmaxf(s_tile[0][r], s_tile[1][r]),
-                                 fmaxf(s_tile[2][r], s_tile[3][r]));
+        for (int r = 0; r < 4; ++r) {
+            float mx = fmaxf(fmaxf(s_tile[0][r], s_tile[1][r]),
+                             fmaxf(s_tile[2][r], s_tile[3][r]));
 #pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {
-                    mx = fmaxf(mx, __shfl_xor(mx, off, WAVE_SIZE));
-                }
-                m_new[r] = fmaxf(m_run[mt][r], mx);
+            for (int off = 1; off < 16; off <<= 1) {
+                mx = fmaxf(mx, __shfl_xor(mx, off, WAVE_SIZE));
             }
-            float rescale[4];
+            m_new[r] = fmaxf(m_run[r], mx);
+        }
+        float rescale[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                rescale[r] = __expf(m_run[mt][r] - m_new[r]);
-                m_run[mt][r] = m_new[r];
-                l_run[mt][r] *= rescale[r];
-            }
+        for (int r = 0; r < 4; ++r) {
+            rescale[r] = __expf(m_run[r] - m_new[r]);
+            m_run[r] = m_new[r];
+            l_run[r] *= rescale[r];
+        }
 #pragma unroll
-            for (int s = 0; s < DSUB; ++s) {
+        for (int s = 0; s < DSUB; ++s) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) accO[mt][s][r] *= rescale[r];
-            }
+            for (int r = 0; r < 4; ++r) accO[s][r] *= rescale[r];
+        }
 
-            // P = exp(S - m); stage bf16 for the PV mfma; accumulate l
+        // P = exp(S - m); stage bf16 for the PV mfma; accumulate l
 #pragma unroll
-            for (int ns = 0; ns < 4; ++ns) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pv = __expf(s_tile[ns][r] - m_run[mt][r]);
-                    s_tile[ns][r] = pv;
-                    p_lds[wave][(mt * 16 + 4 * lgrp + r) * VSTRIDE + ns * 16 + lcol] =
-                        (bf16)pv;
-                }
-            }
+        for (int ns = 0; ns < 4; ++ns) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float ls = s_tile[0][r] + s_tile[1][r] + s_tile[2][r] + s_tile[3][r];
-#pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {
-                    ls += __shfl_xor(ls, off, WAVE_SIZE);
-                }
-                l_run[mt][r] += ls;
+                float pv = __expf(s_tile[ns][r] - m_run[r]);
+                s_tile[ns][r] = pv;
+                p_lds[wave][(4 * lgrp + r) * VSTRIDE + ns * 16 + lcol] = (bf16)pv;
             }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float ls = s_tile[0][r] + s_tile[1][r] + s_tile[2][r] + s_tile[3][r];
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {
+                ls += __shfl_xor(ls, off, WAVE_SIZE);
+            }
+            l_run[r] += ls;
         }
         __builtin_amdgcn_s_waitcnt(0);  // own-wave P writes visible
 
         // O += P V  (K = 64 in 2 chunks of 32)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
+        for (int kc = 0; kc < 2; ++kc) {
+            frag_ab aP = *reinterpret_cast<const frag_ab*>(
+                &p_lds[wave][lcol * VSTRIDE + kc * 32 + 8 * lgrp]);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int kc = 0; kc < 2; ++kc) {
-                frag_ab aP = *reinterpret_cast<const frag_ab*>(
-                    &p_lds[wave][(mt * 16 + lcol) * VSTRIDE + kc * 32 + 8 * lgrp]);
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int ds = 0; ds < DSUB; ++ds) {
-                    frag_ab bV = *reinterpret_cast<const frag_ab*>(
-                        &vt_lds[(ds * 16 + lcol) * VSTRIDE + kc * 32 + 8 * lgrp]);
-                    accO[mt][ds] = MFMA_16x16x32(aP, bV, accO[mt][ds]);
-                }
-                __builtin_amdgcn_s_setprio(0);
+            for (int ds = 0; ds < DSUB; ++ds) {
+                frag_ab bV = *reinterpret_cast<const frag_ab*>(
+                    &vt_lds[(ds * 16 + lcol) * VSTRIDE + kc * 32 + 8 * lgrp]);
+                accO[ds] = MFMA_16x16x32(aP, bV, accO[ds]);
             }
+            __builtin_amdgcn_s_setprio(0);
         }
     }
 
     // epilogue
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int iq = qrow0 + mt * 16 + 4 * lgrp + r;
-            const float inv_l = 1.0f / l_run[mt][r];
-            bf16* orow = op + (int64_t)iq * os;
-#pragma unroll
-            for (int ds = 0; ds < DSUB; ++ds) {
-                orow[ds * 16 + lcol] = (bf16)(accO[mt][ds][r] * inv_l);
-            }
-            if (lcol == 0) {
-                lse[bh_off + iq] = m_run[mt][r] + __logf(l_run[mt][r]);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------ probe
-// Verifies the assumed A/B fragment layouts: C[16][16] = A[16][32]·B[32][16]
-// with A,B read from global memory exactly the way the attention kernel
-// reads its fragments.  One wave.
-__global__ void mfma_probe_kernel(const bf16* __restrict__ A,
-                                  const bf16* __restrict__ Bt,
-                                  float* __restrict__ C) {
-    const int lane = threadIdx.x;
-    const int lgrp = lane >> 4, lcol = lane & 15;
-    // A[m][k]: m = lcol, k = 8*lgrp + i  (row-major A: 16x32)
-    frag_ab a = *reinterpret_cast<const frag_ab*>(A + lcol * 32 + 8 * lgrp);
-    // B[k][n] with Bt stored as [n][k] (row-major 16x32): n = lcol, k = 8*lgrp+i
-    frag_ab b = *reinterpret_cast<const frag_ab*>(Bt + lcol * 32 + 8 * lgrp);
-    frag_cd c = MFMA_16x16x32(a, b, frag_cd{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
     for (int r = 0; r < 4; ++r) {
-        C[(4 * lgrp + r) * 16 + lcol] = c[r];
+        const int iq = qrow0 + 4 * lgrp + r;
+        const float inv_l = 1.0f / l_run[r];
+        bf16* orow = op + (int64_t)iq * os;
+#pragma unroll
+        for (int ds = 0; ds < DSUB; ++ds) {
+            orow[ds * 16 + lcol] = (bf16)(accO[ds][r] * inv_l);
+        }
+        if (lcol == 0) {
+            lse[bh_off + iq] = m_run[r] + __logf(l_run[r]);
+        }
     }
 }
 
 }  // namespace
 
 // ======================================================================
-// Forward v2 — the round-2 speed-of-light ladder (docs/KERNEL_PLAN_R2.md):
-//   * 8 waves x 32 q rows, v_mfma_f32_32x32x16_bf16 (guide §B 8-warp ladder)
+// Forward v2 (docs/KERNEL_PLAN_R2.md):
+//   * 4 or 8 waves x 32 q rows, v_mfma_f32_32x32x16_bf16 (guide §B 8-warp ladder)
 //   * swapped QK^T (St = K·Q^T): the P row for q-row lane&31 is lane-local
 //     (32 f32 regs), so softmax is in-register — no p_lds bounce, no
 //     __shfl tree (T12: cross-half combine = one permlane32_swap)
@@ -291,15 +267,6 @@ __global__ void mfma_probe_kernel(const bf16* __restrict__ A,
 __device__ __forceinline__ float u2f(unsigned u) { return __uint_as_float(u); }
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using lds_bf16x4_p = __attribute__((address_space(3))) bf16x4*;
-
-__device__ __forceinline__ f32x16 MFMA_32x32x16(frag_ab a, frag_ab b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 // Element index into a swizzled [row][128] bf16 image (256-B rows): the
 // byte offset within the row is XORed with (row&15)<<4, spreading a b128
@@ -667,209 +634,22 @@ void attn_fwd_v2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
     }
 }
 
-// semantics probe for ds_read_b64_tr_b16: stage a [4][16] bf16 tile into
-// LDS, read it with the transpose instruction the way the PV loop does,
-// and write out what each lane received (expected: lane l&15 gets column
-// l&15, elements j=0..3 = rows).
-__global__ void tr16_probe_kernel(const bf16* __restrict__ in,
-                                  float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) bf16 lds[64];
-    const int lane = threadIdx.x;
-    if (lane < 8) {
-        *reinterpret_cast<frag_ab*>(&lds[lane * 8]) =
-            *reinterpret_cast<const frag_ab*>(in + lane * 8);
-    }
-    __syncthreads();
-    if (lane < 16) {
-        bf16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (lds_bf16x4_p)&lds[lane * 4]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[lane * 4 + j] = (float)v[j];
-    }
-}
-
-// layout probe for the 32x32x16 fragment maps (see attn_fwd_v2_kernel)
-__global__ void mfma_probe32_kernel(const bf16* __restrict__ A,
-                                    const bf16* __restrict__ Bt,
-                                    float* __restrict__ C) {
-    const int lane = threadIdx.x;
-    const int l31 = lane & 31, hi = lane >> 5;
-    // A[i][k]: i = l31, k = 8*hi + e (row-major A: 32x16)
-    frag_ab a = *reinterpret_cast<const frag_ab*>(A + l31 * 16 + 8 * hi);
-    // B[k][j] with Bt stored [j][k] (row-major 32x16): j = l31, k = 8*hi + e
-    frag_ab b = *reinterpret_cast<const frag_ab*>(Bt + l31 * 16 + 8 * hi);
-    f32x16 c;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) c[r] = 0.f;
-    c = MFMA_32x32x16(a, b, c);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        C[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = c[r];
-    }
-}
-
 }  // namespace
 
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor slopes,
-                                    double scale, int64_t kv_off) {
-    TORCH_CHECK(q.is_cuda() && q.stride(3) == 1 && k.stride(3) == 1 &&
-                v.stride(3) == 1, "attn_fwd: last dim must be contiguous");
-    TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_fwd: bf16 only");
-    const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-    const int Hkv = k.size(1);
-    TORCH_CHECK(H % Hkv == 0, "attn_fwd: q heads must be a multiple of kv heads");
-    const int kv_group = H / Hkv;
-    TORCH_CHECK(S % BLOCK_M == 0, "attn_fwd: S must be a multiple of 64");
-    TORCH_CHECK(D == 64 || D == 128, "attn_fwd: head dim 64 or 128");
-    TORCH_CHECK(slopes.numel() == H && slopes.scalar_type() == torch::kFloat);
-
-    // O physically [B, S, H, D]: the model reshapes attention output back to
-    // [B, S, H*D] for the dense projection — this layout makes that free.
-    auto o_phys = torch::empty({B, S, H, D}, q.options());
-    auto o = o_phys.permute({0, 2, 1, 3});
-    auto lse = torch::empty({B, H, S}, q.options().dtype(torch::kFloat));
-
-    auto stream = at::cuda::getCurrentCUDAStream();
-
-    // v2 (8-wave 32x32-MFMA ladder kernel) handles S % 128 == 0; v1 covers
-    // the rest.  PG_ATTN_V2=0 forces the v1 path for A/B comparisons.
-    static const int use_v2 = [] {
-        const char* e = getenv("PG_ATTN_V2");
-        return e ? atoi(e) : 1;
-    }();
-    // PG_ATTN_W4=1: 4-wave workgroups (two independent WGs per CU instead
-    // of one barrier-locked 8-wave WG — A/B for phase overlap)
-    static const int force_w4 = [] {
-        const char* e = getenv("PG_ATTN_W4");
-        return e ? atoi(e) : 0;
-    }();
-    if (use_v2 && S % 128 == 0) {
-#define LAUNCH_FWD2(DV, WV)                                                   \
-    do {                                                                      \
-        dim3 grid(S / (32 * WV), H, B);                                       \
-        hipLaunchKernelGGL((attn_fwd_v2_kernel<DV, WV>), grid,                \
-            dim3(WV * WAVE_SIZE), 0, stream,                                  \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            slopes.data_ptr<float>(), (float)scale,                           \
-            reinterpret_cast<bf16*>(o_phys.data_ptr()), lse.data_ptr<float>(),\
-            B, H, S, (int)kv_off, kv_group,                                   \
-            q.stride(0), q.stride(1), q.stride(2),                            \
-            k.stride(0), k.stride(1), k.stride(2),                            \
-            v.stride(0), v.stride(1), v.stride(2),                            \
-            o.stride(0), o.stride(1), o.stride(2));                           \
-    } while (0)
-        if (D == 64) {
-            if (S % 256 == 0 && !force_w4) LAUNCH_FWD2(64, 8);
-            else LAUNCH_FWD2(64, 4);
-        } else {
-            if (S % 256 == 0 && !force_w4) LAUNCH_FWD2(128, 8);
-            else LAUNCH_FWD2(128, 4);
-        }
-#undef LAUNCH_FWD2
-        HIP_CHECK_LAUNCH();
-        return {o, lse};
-    }
-
-    // MT=2 (128 q rows / workgroup) when S allows: 2x the MFMA work per LDS
-    // fragment read
-    // D=64: 4 waves x 2 row-tiles.  D=128: default 8 waves x 1 tile
-    // (same 128 q rows, lower per-wave registers); PG_ATTN_V128 picks the
-    // variant (1: 4w/MT1, 2: 4w/MT2, 3: 8w/MT1).
-    static const int v128 = [] {
-        const char* e = getenv("PG_ATTN_V128");
-        return e ? atoi(e) : 3;  // 8-wave MT1: 181 TF vs 153 (4-wave MT2) measured
-    }();
-#define LAUNCH_FWD(DV, MTV, WV)                                               \
-    do {                                                                      \
-        dim3 grid(S / (16 * MTV * WV), H, B);                                 \
-        hipLaunchKernelGGL((attn_fwd_kernel<DV, MTV, WV>), grid,              \
-            dim3(WV * WAVE_SIZE), 0, stream,                                  \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            slopes.data_ptr<float>(), (float)scale,                           \
-            reinterpret_cast<bf16*>(o_phys.data_ptr()), lse.data_ptr<float>(),\
-            B, H, S, (int)kv_off, kv_group,                                   \
-            q.stride(0), q.stride(1), q.stride(2),                            \
-            k.stride(0), k.stride(1), k.stride(2),                            \
-            v.stride(0), v.stride(1), v.stride(2),                            \
-            o.stride(0), o.stride(1), o.stride(2));                           \
-    } while (0)
-    static const int v64 = [] {
-        const char* e = getenv("PG_ATTN_V64");
-        return e ? atoi(e) : 3;  // 8w/MT1: 141 TF vs 135 (4w/MT2) measured
-    }();
-    if (D == 64) {
-        if (S % 128 != 0) LAUNCH_FWD(64, 1, 4);
-        else if (v64 == 3) LAUNCH_FWD(64, 1, 8);
-        else LAUNCH_FWD(64, 2, 4);
-    } else if (S % 128 != 0) {
-        LAUNCH_FWD(128, 1, 4);
-    } else if (v128 == 3) {
-        LAUNCH_FWD(128, 1, 8);
-    } else if (v128 == 2) {
-        LAUNCH_FWD(128, 2, 4);
-    } else {
-        LAUNCH_FWD(128, 1, 4);
-    }
-#undef LAUNCH_FWD
-    HIP_CHECK_LAUNCH();
-    return {o, lse};
-}
-
-torch::Tensor tr16_probe(torch::Tensor tile) {
-    TORCH_CHECK(tile.is_cuda() && tile.scalar_type() == torch::kBFloat16 &&
-                tile.numel() == 64);
-    auto out = torch::empty({16, 4}, tile.options().dtype(torch::kFloat));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 0, stream,
-        reinterpret_cast<const bf16*>(tile.contiguous().data_ptr()),
-        out.data_ptr<float>());
-    HIP_CHECK_LAUNCH();
-    return out;
-}
-
-torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt) {
-    TORCH_CHECK(A.is_cuda() && A.scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(A.sizes() == torch::IntArrayRef({32, 16}) &&
-                Bt.sizes() == torch::IntArrayRef({32, 16}));
-    auto C = torch::empty({32, 32}, A.options().dtype(torch::kFloat));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(mfma_probe32_kernel, dim3(1), dim3(64), 0, stream,
-        reinterpret_cast<const bf16*>(A.contiguous().data_ptr()),
-        reinterpret_cast<const bf16*>(Bt.contiguous().data_ptr()),
-        C.data_ptr<float>());
-    HIP_CHECK_LAUNCH();
-    return C;
-}
-
-torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt) {
-    TORCH_CHECK(A.is_cuda() && A.scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(A.sizes() == torch::IntArrayRef({16, 32}) &&
-                Bt.sizes() == torch::IntArrayRef({16, 32}));
-    auto C = torch::empty({16, 16}, A.options().dtype(torch::kFloat));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, stream,
-        reinterpret_cast<const bf16*>(A.contiguous().data_ptr()),
-        reinterpret_cast<const bf16*>(Bt.contiguous().data_ptr()),
-        C.data_ptr<float>());
-    HIP_CHECK_LAUNCH();
-    return C;
-}
-
 // ======================================================================
-// Backward — two-pass flash2 (no atomics):
-//   delta:  delta[m] = rowsum(dO * O)
+// Backward v1 — two-pass flash2 (no atomics):
+//   delta:  delta[m] = rowsum(dO * O)   (shared with the v2 backward)
 //   pass A (kv-outer): dK, dV — one workgroup per 64-row kv block,
 //                      iterating q blocks >= kv block (causal)
 //   pass B (q-outer):  dQ — one workgroup per 64-row q block,
 //                      iterating kv blocks <= q block
 // Both passes recompute S and P from (q, k, lse): MFMA FLOPs are cheap
-// next to re-reading P from HBM.
+// next to re-reading P from HBM.  Each stages BWD_CHUNK rows of the other
+// axis per iteration (64-row chunks LDS-capped the kernels to one
+// wave/SIMD).
 namespace {
+
+constexpr int BWD_CHUNK = 32;
 
 template <int D>
 __global__ __launch_bounds__(256)
@@ -896,12 +676,8 @@ void attn_bwd_delta_kernel(const bf16* __restrict__ dout,
 }
 
 // pass A: dK(n,:) = scale * sum_m dS(m,n) Q(m,:);  dV(n,:) = sum_m P(m,n) dO(m,:)
-// QR = q rows staged per iteration: 32 keeps LDS under 1/3 of the 160 KB CU
-// budget (at QR=64 the kernel was LDS-capped to ONE wave/SIMD).
-// W = waves per workgroup: 8 waves own 128 kv rows and SHARE each staged
-// q-chunk, halving the Q/dO staging traffic vs 4-wave blocks.
-template <int D, int QR, int W>
-__global__ __launch_bounds__(W * WAVE_SIZE)
+template <int D>
+__global__ __launch_bounds__(NWAVES * WAVE_SIZE)
 void attn_bwd_dkdv_kernel(const bf16* __restrict__ dout,
                           const bf16* __restrict__ q, const bf16* __restrict__ k,
                           const bf16* __restrict__ v,
@@ -917,22 +693,20 @@ void attn_bwd_dkdv_kernel(const bf16* __restrict__ dout,
                           int64_t wb, int64_t wh, int64_t ws) {
     constexpr int DCH = D / 32;
     constexpr int DSUB = D / 16;
-    constexpr int NT = W * WAVE_SIZE;
-    constexpr int KVROWS = W * 16;     // kv rows per workgroup
+    constexpr int NT = NWAVES * WAVE_SIZE;
+    constexpr int QR = BWD_CHUNK;      // q rows staged per iteration
+    constexpr int KVROWS = BLOCK_M;    // kv rows per workgroup
 
-    // round-2 retrofit: power-of-2 row strides with the T2 XOR swizzle
-    // (row-major tiles on 256-B rows via swz128 for D=128 — 128-B rows via
-    // swz64 for D=64, keeping the LDS footprint and occupancy of r1 —
-    // transposed tiles on 128-B rows via swz64) replace the +8-element
-    // padding: r1 PMC measured 33-63% of LDS cycles in bank conflicts.
+    // tile layouts: see bwd_rm / bwd_tr (swizzled power-of-2 rows at D=128,
+    // padded odd strides at D=64)
     constexpr int RMS = (D == 64) ? 72 : 128;   // row-major tile stride
     constexpr int TRS = (D == 64) ? 40 : 64;    // transposed tile stride
     __shared__ bf16 do_lds[QR * RMS];
     __shared__ bf16 q_lds[QR * RMS];
     __shared__ bf16 qt_lds[D * TRS];
     __shared__ bf16 dot_lds[D * TRS];
-    __shared__ bf16 pt_lds[W][16 * TRS];   // P^T  (n rows, m cols)
-    __shared__ bf16 dst_lds[W][16 * TRS];  // dS^T (n rows, m cols)
+    __shared__ bf16 pt_lds[NWAVES][16 * TRS];   // P^T  (n rows, m cols)
+    __shared__ bf16 dst_lds[NWAVES][16 * TRS];  // dS^T (n rows, m cols)
     __shared__ float lse_lds[QR];
     __shared__ float delta_lds[QR];
 
@@ -1077,10 +851,8 @@ void attn_bwd_dkdv_kernel(const bf16* __restrict__ dout,
 }
 
 // pass B: dQ(m,:) = scale * sum_n dS(m,n) K(n,:)
-// KVR = kv rows staged per iteration (same LDS-occupancy reasoning as QR);
-// W waves (8 when S allows) share each staged kv chunk.
-template <int D, int KVR, int W>
-__global__ __launch_bounds__(W * WAVE_SIZE)
+template <int D>
+__global__ __launch_bounds__(NWAVES * WAVE_SIZE)
 void attn_bwd_dq_kernel(const bf16* __restrict__ dout,
                         const bf16* __restrict__ q, const bf16* __restrict__ k,
                         const bf16* __restrict__ v,
@@ -1096,16 +868,17 @@ void attn_bwd_dq_kernel(const bf16* __restrict__ dout,
                         int64_t wb, int64_t wh, int64_t ws) {
     constexpr int DCH = D / 32;
     constexpr int DSUB = D / 16;
-    constexpr int NT = W * WAVE_SIZE;
-    constexpr int QROWS = W * 16;          // q rows per workgroup
+    constexpr int NT = NWAVES * WAVE_SIZE;
+    constexpr int KVR = BWD_CHUNK;         // kv rows staged per iteration
+    constexpr int QROWS = BLOCK_M;         // q rows per workgroup
 
-    // swizzled strides, same scheme as dkdv (see comment there)
+    // same tile strides as dkdv
     constexpr int RMS = (D == 64) ? 72 : 128;
     constexpr int TRS = (D == 64) ? 40 : 64;
     __shared__ bf16 k_lds[KVR * RMS];       // row-major K (QK^T B-frags)
     __shared__ bf16 v_lds[KVR * RMS];       // row-major V (dP B-frags)
     __shared__ bf16 kt_lds[D * TRS];        // transposed K (dQ B-frags)
-    __shared__ bf16 ds_lds[W][16 * TRS];    // dS (m rows, n cols)
+    __shared__ bf16 ds_lds[NWAVES][16 * TRS];  // dS (m rows, n cols)
 
     const int qb = blockIdx.x;
     const int h = blockIdx.y;
@@ -1862,176 +1635,205 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
 
 }  // namespace
 
+// ======================================================================
+// Host side: one selection table, one argument check, one launcher.
+namespace {
+
+struct AttnVariant {
+    bool v2;     // the 32x32-MFMA kernels; false = the v1 fallback
+    int waves;   // per workgroup
+    int rows() const { return waves * (v2 ? 32 : 16); }  // per workgroup
+};
+
+// The selection table of the file header.  Forward and backward both launch
+// what this returns, so they always tile a problem the same way.
+AttnVariant select_variant(int64_t S, int64_t D) {
+    TORCH_CHECK(D == 64 || D == 128,
+                "attention: head dim must be 64 or 128, got ", D);
+    TORCH_CHECK(S > 0 && S % 64 == 0,
+                "attention: S must be a positive multiple of 64, got ", S);
+    if (S % 128 != 0) return {false, 4};
+    if (S % 256 != 0) return {true, 4};
+    return {true, 8};
+}
+
+// a bf16 [.,.,.,D] device tensor of the given sizes, d contiguous
+void check_operand(const char* who, const char* name, const torch::Tensor& t,
+                   torch::IntArrayRef sizes) {
+    TORCH_CHECK(t.is_cuda(), who, ": ", name, " must be on the GPU");
+    TORCH_CHECK(t.scalar_type() == torch::kBFloat16, who, ": ", name,
+                " must be bf16");
+    TORCH_CHECK(t.sizes() == sizes, who, ": ", name, " has sizes ", t.sizes(),
+                ", expected ", sizes);
+    TORCH_CHECK(t.stride(3) == 1, who, ": last dim of ", name,
+                " must be contiguous");
+}
+
+struct AttnDims {
+    int B, H, Hkv, S, D;
+    AttnVariant var;
+};
+
+// What every kernel assumes about q, k, v and slopes; shared by attn_fwd and
+// attn_bwd_into, and done before anything is launched.
+AttnDims check_qkv(const char* who, const torch::Tensor& q,
+                   const torch::Tensor& k, const torch::Tensor& v,
+                   const torch::Tensor& slopes) {
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4, who,
+                ": q and k must be [B, H, S, D]");
+    const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+    const int64_t Hkv = k.size(1);
+    check_operand(who, "q", q, {B, H, S, D});
+    check_operand(who, "k", k, {B, Hkv, S, D});
+    check_operand(who, "v", v, {B, Hkv, S, D});
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, who,
+                ": q heads must be a multiple of kv heads");
+    TORCH_CHECK(slopes.is_cuda() && slopes.scalar_type() == torch::kFloat &&
+                slopes.numel() == H && slopes.is_contiguous(), who,
+                ": slopes must be ", H, " contiguous fp32 values on the GPU");
+    return {(int)B, (int)H, (int)Hkv, (int)S, (int)D, select_variant(S, D)};
+}
+
+const bf16* bf16_in(const torch::Tensor& t) {
+    return reinterpret_cast<const bf16*>(t.data_ptr());
+}
+bf16* bf16_out(const torch::Tensor& t) {
+    return reinterpret_cast<bf16*>(t.data_ptr());
+}
+// batch, head and row strides, in the order every kernel takes them
+std::tuple<int64_t, int64_t, int64_t> strides3(const torch::Tensor& t) {
+    return {t.stride(0), t.stride(1), t.stride(2)};
+}
+
+// Launches `kernel` on `waves`-wave workgroups; `args` is a tuple in the
+// kernel's parameter order.
+template <typename... P, typename Args>
+void launch(void (*kernel)(P...), dim3 grid, int waves, hipStream_t stream,
+            const Args& args) {
+    static_assert(sizeof...(P) == std::tuple_size<Args>::value,
+                  "argument pack does not match the kernel's parameters");
+    std::apply([&](auto... a) {
+        hipLaunchKernelGGL(kernel, grid, dim3(waves * WAVE_SIZE), 0, stream,
+                           static_cast<P>(a)...);
+    }, args);
+}
+
+// Calls f(integral_constant<D>, integral_constant<waves>): the one place
+// where the runtime head dim and wave count become template arguments.
+template <typename F>
+void with_d_waves(int D, int waves, F&& f) {
+    auto with_waves = [&](auto d) {
+        if (waves == 8) f(d, std::integral_constant<int, 8>{});
+        else f(d, std::integral_constant<int, 4>{});
+    };
+    if (D == 64) with_waves(std::integral_constant<int, 64>{});
+    else with_waves(std::integral_constant<int, 128>{});
+}
+
+}  // namespace
+
+std::tuple<std::string, int64_t> attn_variant(int64_t S, int64_t D) {
+    const AttnVariant var = select_variant(S, D);
+    return {var.v2 ? "v2" : "v1", var.waves};
+}
+
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, torch::Tensor slopes,
+                                    double scale, int64_t kv_off) {
+    const AttnDims d = check_qkv("attn_fwd", q, k, v, slopes);
+
+    // O physically [B, S, H, D]: the model reshapes attention output back to
+    // [B, S, H*D] for the dense projection — this layout makes that free.
+    auto o_phys = torch::empty({d.B, d.S, d.H, d.D}, q.options());
+    auto o = o_phys.permute({0, 2, 1, 3});
+    auto lse = torch::empty({d.B, d.H, d.S}, q.options().dtype(torch::kFloat));
+
+    const auto args = std::tuple_cat(
+        std::make_tuple(bf16_in(q), bf16_in(k), bf16_in(v),
+                        slopes.data_ptr<float>(), (float)scale,
+                        bf16_out(o_phys), lse.data_ptr<float>(),
+                        d.B, d.H, d.S, (int)kv_off, d.H / d.Hkv),
+        strides3(q), strides3(k), strides3(v), strides3(o));
+    const dim3 grid(d.S / d.var.rows(), d.H, d.B);
+    auto stream = at::cuda::getCurrentCUDAStream();
+    with_d_waves(d.D, d.var.waves, [&](auto dv_, auto wv_) {
+        constexpr int DV = decltype(dv_)::value, WV = decltype(wv_)::value;
+        if (d.var.v2) launch(attn_fwd_v2_kernel<DV, WV>, grid, WV, stream, args);
+        else launch(attn_fwd_kernel<DV>, grid, WV, stream, args);
+    });
+    HIP_CHECK_LAUNCH();
+    return {o, lse};
+}
+
 void attn_bwd_into(torch::Tensor dout, torch::Tensor q,
                    torch::Tensor k, torch::Tensor v,
                    torch::Tensor o, torch::Tensor lse,
                    torch::Tensor slopes, double scale,
                    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                    int64_t kv_off) {
-    TORCH_CHECK(dout.is_cuda() && dout.stride(3) == 1 && q.stride(3) == 1 &&
-                k.stride(3) == 1 && v.stride(3) == 1 && o.stride(3) == 1,
-                "attn_bwd: last dim must be contiguous");
-    TORCH_CHECK(dq.stride(3) == 1 && dk.stride(3) == 1 && dv.stride(3) == 1);
+    const AttnDims d = check_qkv("attn_bwd", q, k, v, slopes);
+    check_operand("attn_bwd", "dout", dout, q.sizes());
+    check_operand("attn_bwd", "o", o, q.sizes());
+    check_operand("attn_bwd", "dq", dq, q.sizes());
+    check_operand("attn_bwd", "dk", dk, k.sizes());
+    check_operand("attn_bwd", "dv", dv, k.sizes());
     // dk and dv must share a stride layout (one stride set feeds both writes)
-    TORCH_CHECK(dk.strides() == dv.strides());
-    const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-    const int Hkv = k.size(1);
-    TORCH_CHECK(H % Hkv == 0);
-    const int kv_group = H / Hkv;
-    auto delta = torch::empty({B, H, S}, q.options().dtype(torch::kFloat));
+    TORCH_CHECK(dk.strides() == dv.strides(),
+                "attn_bwd: dk and dv must have the same strides");
+    TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat &&
+                lse.sizes() == torch::IntArrayRef({d.B, d.H, d.S}) &&
+                lse.is_contiguous(),
+                "attn_bwd: lse must be contiguous fp32 [B, H, S] on the GPU");
+    auto delta = torch::empty({d.B, d.H, d.S},
+                              q.options().dtype(torch::kFloat));
 
-    const int64_t rows = (int64_t)B * H * S;
+    const int64_t rows = (int64_t)d.B * d.H * d.S;
+    const auto delta_args = std::tuple_cat(
+        std::make_tuple(bf16_in(dout), bf16_in(o), delta.data_ptr<float>(),
+                        rows, d.H, d.S),
+        strides3(dout), strides3(o));
+    // dq and dkdv kernels differ only in their outputs and output strides
+    const auto inputs = std::make_tuple(
+        bf16_in(dout), bf16_in(q), bf16_in(k), bf16_in(v),
+        lse.data_ptr<float>(), delta.data_ptr<float>(),
+        slopes.data_ptr<float>(), (float)scale);
+    const auto dims_strides = std::tuple_cat(
+        std::make_tuple(d.B, d.H, d.S, (int)kv_off, d.H / d.Hkv),
+        strides3(dout), strides3(q), strides3(k), strides3(v));
+    const auto dq_args = std::tuple_cat(
+        inputs, std::make_tuple(bf16_out(dq)), dims_strides, strides3(dq));
+    const auto dkdv_args = std::tuple_cat(
+        inputs, std::make_tuple(bf16_out(dk), bf16_out(dv)), dims_strides,
+        strides3(dk));
+
+    const dim3 grid_delta((rows + 3) / 4);
+    const dim3 grid_q(d.S / d.var.rows(), d.H, d.B);
+    const dim3 grid_kv(d.S / d.var.rows(), d.Hkv, d.B);
     auto stream = at::cuda::getCurrentCUDAStream();
-
-    // v2 path (32x32 MFMA, lane-local stats, tr16 transposed reads)
-    static const int use_bwd_v2 = [] {
-        const char* e = getenv("PG_ATTN_BWD_V2");
-        return e ? atoi(e) : 1;
-    }();
-    // measured (r2h A/B): v2 wins at both head dims once the sub-tile loops
-    // stopped unrolling (D=64: 1264 -> 1110 us; D=128: 5448 -> 5153 us on
-    // the bench shapes); PG_ATTN_BWD_V2=0 forces the v1 kernels
-    if (use_bwd_v2 && S % 128 == 0 && (D == 64 || D == 128)) {
-#define STRV(t) t.stride(0), t.stride(1), t.stride(2)
-#define BWD2_ARGS(W_OUT)                                                      \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            lse.data_ptr<float>(), delta.data_ptr<float>(),                   \
-            slopes.data_ptr<float>(), (float)scale, W_OUT,                    \
-            B, H, S, (int)kv_off, kv_group,                                   \
-            STRV(dout), STRV(q), STRV(k), STRV(v), STRV(dq)
-#define LAUNCH_DELTA(DV)                                                      \
-        hipLaunchKernelGGL((attn_bwd_delta_kernel<DV>),                       \
-            dim3((rows + 3) / 4), dim3(256), 0, stream,                       \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(o.data_ptr()),                      \
-            delta.data_ptr<float>(), rows, H, S, STRV(dout), STRV(o))
-#define LAUNCH_DQ2(DV, WV)                                                    \
-    do {                                                                      \
-        dim3 grid_q(S / (32 * WV), H, B);                                     \
-        hipLaunchKernelGGL((attn_bwd_dq_v2_kernel<DV, WV>), grid_q,           \
-            dim3(WV * WAVE_SIZE), 0, stream,                                  \
-            BWD2_ARGS(reinterpret_cast<bf16*>(dq.data_ptr())));               \
-    } while (0)
-#define LAUNCH_BWD2(DV, WV, DKV, DVV, DKP)                                         \
-    do {                                                                      \
-        dim3 grid_kv(S / (32 * WV), Hkv, B);                                  \
-        hipLaunchKernelGGL((attn_bwd_dkdv_v2_kernel<DV, WV, DKV, DVV, DKP>), \
-            grid_kv,                                                          \
-            dim3(WV * WAVE_SIZE), 0, stream,                                  \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            lse.data_ptr<float>(), delta.data_ptr<float>(),                   \
-            slopes.data_ptr<float>(), (float)scale,                           \
-            reinterpret_cast<bf16*>(dk.data_ptr()),                           \
-            reinterpret_cast<bf16*>(dv.data_ptr()),                           \
-            B, H, S, (int)kv_off, kv_group,                                   \
-            STRV(dout), STRV(q), STRV(k), STRV(v), STRV(dk));                 \
-    } while (0)
-        // D=64 fits the fused dk+dv kernel in 2 waves/SIMD; D=128 would
-        // spill, so it runs as a dv-only and a dk-only pass (St recomputed,
-        // +25% MFMA but no scratch traffic)
-        static const int force_w4b = [] {
-            const char* e = getenv("PG_ATTN_W4");
-            return e ? atoi(e) : 0;
-        }();
-        if (D == 64) {
-            LAUNCH_DELTA(64);
-            if (S % 256 == 0 && !force_w4b) {
-                LAUNCH_DQ2(64, 8);
-                LAUNCH_BWD2(64, 8, true, true, -1);
-            } else {
-                LAUNCH_DQ2(64, 4);
-                LAUNCH_BWD2(64, 4, true, true, -1);
-            }
-        } else {
-            // fused dk+dv spills at D=128 (256+144 regs wanted); run as a
-            // dv-only pass plus two half-width dk passes, all 8-wave
-            LAUNCH_DELTA(128);
-            if (S % 256 == 0) {
-                LAUNCH_DQ2(128, 8);
-                LAUNCH_BWD2(128, 8, false, true, -1);
-                LAUNCH_BWD2(128, 8, true, false, 0);
-                LAUNCH_BWD2(128, 8, true, false, 1);
-            } else {
-                LAUNCH_DQ2(128, 4);
-                LAUNCH_BWD2(128, 4, false, true, -1);
-                LAUNCH_BWD2(128, 4, true, false, 0);
-                LAUNCH_BWD2(128, 4, true, false, 1);
-            }
+    with_d_waves(d.D, d.var.waves, [&](auto dv_, auto wv_) {
+        constexpr int DV = decltype(dv_)::value, WV = decltype(wv_)::value;
+        launch(attn_bwd_delta_kernel<DV>, grid_delta, 4, stream, delta_args);
+        if (!d.var.v2) {
+            launch(attn_bwd_dkdv_kernel<DV>, grid_kv, WV, stream, dkdv_args);
+            launch(attn_bwd_dq_kernel<DV>, grid_q, WV, stream, dq_args);
+            return;
         }
-#undef LAUNCH_BWD2
-#undef LAUNCH_DQ2
-#undef LAUNCH_DELTA
-#undef BWD2_ARGS
-#undef STRV
-        HIP_CHECK_LAUNCH();
-        return;
-    }
-
-    const int dkdv_waves = (S % 128 == 0) ? 8 : 4;
-    dim3 grid_a(S / (16 * dkdv_waves), Hkv, B);
-    dim3 grid_b(S / (16 * dkdv_waves), H, B);
-
-#define STR3(t) t.stride(0), t.stride(1), t.stride(2)
-#define BWD_DKDV_ARGS                                                         \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            lse.data_ptr<float>(), delta.data_ptr<float>(),                   \
-            slopes.data_ptr<float>(), (float)scale,                           \
-            reinterpret_cast<bf16*>(dk.data_ptr()),                           \
-            reinterpret_cast<bf16*>(dv.data_ptr()), B, H, S, (int)kv_off,     \
-            kv_group,                                                         \
-            STR3(dout), STR3(q), STR3(k), STR3(v), STR3(dk)
-#define BWD_DQ_ARGS                                                           \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(q.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(k.data_ptr()),                      \
-            reinterpret_cast<const bf16*>(v.data_ptr()),                      \
-            lse.data_ptr<float>(), delta.data_ptr<float>(),                   \
-            slopes.data_ptr<float>(), (float)scale,                           \
-            reinterpret_cast<bf16*>(dq.data_ptr()), B, H, S, (int)kv_off,     \
-            kv_group,                                                         \
-            STR3(dout), STR3(q), STR3(k), STR3(v), STR3(dq)
-#define LAUNCH_BWD(DV)                                                        \
-    do {                                                                      \
-        hipLaunchKernelGGL((attn_bwd_delta_kernel<DV>),                       \
-            dim3((rows + 3) / 4), dim3(256), 0, stream,                       \
-            reinterpret_cast<const bf16*>(dout.data_ptr()),                   \
-            reinterpret_cast<const bf16*>(o.data_ptr()),                      \
-            delta.data_ptr<float>(), rows, H, S, STR3(dout), STR3(o));        \
-        if (dkdv_waves == 8) {                                                \
-            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DV, 32, 8>),             \
-                grid_a, dim3(512), 0, stream, BWD_DKDV_ARGS);                 \
-        } else {                                                              \
-            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DV, 32, 4>),             \
-                grid_a, dim3(256), 0, stream, BWD_DKDV_ARGS);                 \
-        }                                                                     \
-        if (dkdv_waves == 8) {                                                \
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<DV, 32, 8>),               \
-                grid_b, dim3(512), 0, stream, BWD_DQ_ARGS);                   \
-        } else {                                                              \
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<DV, 32, 4>),               \
-                grid_b, dim3(256), 0, stream, BWD_DQ_ARGS);                   \
-        }                                                                     \
-    } while (0)
-
-    if (D == 64) {
-        LAUNCH_BWD(64);
-    } else {
-        TORCH_CHECK(D == 128, "attn_bwd: head dim 64 or 128");
-        LAUNCH_BWD(128);
-    }
-#undef LAUNCH_BWD
-#undef BWD_DKDV_ARGS
-#undef BWD_DQ_ARGS
-#undef STR3
+        launch(attn_bwd_dq_v2_kernel<DV, WV>, grid_q, WV, stream, dq_args);
+        if constexpr (DV == 64) {
+            launch(attn_bwd_dkdv_v2_kernel<64, WV, true, true, -1>,
+                   grid_kv, WV, stream, dkdv_args);
+        } else {
+            // the fused kernel would spill at D=128 (256+144 registers
+            // wanted): a dv-only pass plus two half-width dk passes (St
+            // recomputed, +25% MFMA but no scratch traffic)
+            launch(attn_bwd_dkdv_v2_kernel<128, WV, false, true, -1>,
+                   grid_kv, WV, stream, dkdv_args);
+            launch(attn_bwd_dkdv_v2_kernel<128, WV, true, false, 0>,
+                   grid_kv, WV, stream, dkdv_args);
+            launch(attn_bwd_dkdv_v2_kernel<128, WV, true, false, 1>,
+                   grid_kv, WV, stream, dkdv_args);
+        }
+    });
     HIP_CHECK_LAUNCH();
 }
 

@@ -32,6 +32,7 @@ void attn_bwd_into(torch::Tensor dout, torch::Tensor q,
                    torch::Tensor slopes, double scale,
                    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                    int64_t kv_off);
+std::tuple<std::string, int64_t> attn_variant(int64_t S, int64_t D);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -113,6 +114,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn_bwd_into", &attn_bwd_into,
           "flash attention bwd writing grads into caller buffers "
           "(e.g. fused-qkv gradient slices)");
+    m.def("attn_variant", &attn_variant,
+          "(S, D) -> (kernel family \"v1\"/\"v2\", waves per workgroup): the "
+          "selection table attn_fwd and attn_bwd share; raises on "
+          "unsupported shapes");
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

@@ -8,20 +8,21 @@ from pipegoose_amd.config import RuntimeConfig
 
 def test_defaults_and_env(monkeypatch):
     monkeypatch.setenv("PG_BUCKET_MB", "40")
-    monkeypatch.setenv("PG_ATTN_V2", "0")
+    monkeypatch.setenv("PG_HAND_GEMM", "1")
     cfg = RuntimeConfig.from_env()
     assert cfg.bucket_size_mb == 40
-    assert cfg.attn_v2 == 0
+    assert RuntimeConfig().hand_gemm == 0 and cfg.hand_gemm == 1
     assert cfg.optimizer == "hip"
 
 
 def test_yaml_env_precedence(tmp_path, monkeypatch):
     f = tmp_path / "job.yaml"
-    f.write_text("bucket_size_mb: 50\nattn_v2: 0\noptimizer: foreach\n")
+    f.write_text("bucket_size_mb: 50\nhand_gemm: 1\noptimizer: foreach\n")
     monkeypatch.setenv("PG_BUCKET_MB", "60")  # env beats the file
+    monkeypatch.delenv("PG_HAND_GEMM", raising=False)
     cfg = RuntimeConfig.from_yaml(str(f))
     assert cfg.bucket_size_mb == 60
-    assert cfg.attn_v2 == 0          # file beats default
+    assert RuntimeConfig().hand_gemm == 0 and cfg.hand_gemm == 1  # file beats default
     assert cfg.optimizer == "foreach"
 
 
