@@ -155,6 +155,15 @@ class BloomAttention(nn.Module):
         bias = bias.masked_fill(kpos > pos_t, float("-inf"))  # [H, 1, k_len]
         return bias.to(dtype)[None]
 
+    def _slopes_f32(self, device) -> torch.Tensor:
+        """fp32 slopes on ``device`` for the decode kernel, converted once
+        (not once per captured step)."""
+        cached = getattr(self, "_slopes_f32_cache", None)
+        if cached is None or cached.device != device:
+            cached = self.alibi_slopes.to(device=device, dtype=torch.float32)
+            self._slopes_f32_cache = cached
+        return cached
+
     def forward(self, hidden: torch.Tensor, past_kv=None, use_cache: bool = False):
         B = hidden.size(0)
         fused = self.query_key_value(hidden)  # [B, S, local_heads * 3 * hd]
@@ -178,7 +187,17 @@ class BloomAttention(nn.Module):
         from pipegoose_amd.ops.attention import (alibi_attention,
                                                  alibi_attention_qkv,
                                                  kernel_supported)
-        if present is not None and getattr(present, "graph_mode", False):
+        from pipegoose_amd.ops.decode_attention import (
+            decode_attention, decode_kernel_supported)
+        graph_mode = present is not None and getattr(present, "graph_mode",
+                                                     False)
+        if (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
+            # single-query decode kernel: the position is the cache's device
+            # pos_t in graph mode (read in-kernel), else the last filled slot
+            out = decode_attention(q, k, v, self._slopes_f32(q.device),
+                                   self.inv_norm,
+                                   pos=present.pos_t if graph_mode else None)
+        elif graph_mode:
             # hipGraph-capturable decode: constant shapes (full cache
             # length), position enters as DATA via the cache's device pos_t
             bias = self._alibi_bias_graph(k.size(2), present.pos_t, q.dtype)

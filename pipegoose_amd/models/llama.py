@@ -105,6 +105,15 @@ class LlamaAttention(nn.Module):
             self._mask_cache[key] = m.to(dtype)[None, None]
         return self._mask_cache[key]
 
+    def _slopes_f32(self, device) -> torch.Tensor:
+        """fp32 (all-zero) slopes on ``device`` for the decode kernel,
+        converted once (not once per captured step)."""
+        cached = getattr(self, "_slopes_f32_cache", None)
+        if cached is None or cached.device != device:
+            cached = self.zero_slopes.to(device=device, dtype=torch.float32)
+            self._slopes_f32_cache = cached
+        return cached
+
     def forward(self, hidden: torch.Tensor, past_kv=None,
                 use_cache: bool = False):
         B = hidden.size(0)
@@ -149,6 +158,8 @@ class LlamaAttention(nn.Module):
 
         from pipegoose_amd.ops.attention import (alibi_attention,
                                                  kernel_supported)
+        from pipegoose_amd.ops.decode_attention import (
+            decode_attention, decode_kernel_supported)
         kernel_ok = (kernel_supported(q) and past_kv is None
                      and not use_cache)
         if self._cp_size() > 1 and past_kv is None and not use_cache:
@@ -162,6 +173,13 @@ class LlamaAttention(nn.Module):
                 torch.zeros(self.num_heads, device=q.device),
                 self.inv_norm, parallel_context=self.parallel_context,
                 parallel_mode=ParallelMode.CONTEXT).to(q.dtype)
+        elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
+            # single-query decode kernel over the un-expanded Hkv-head cache
+            # (GQA mapped in-kernel); the position is the cache's device
+            # pos_t in graph mode, else the last filled slot
+            out = decode_attention(q, k, v, self._slopes_f32(q.device),
+                                   self.inv_norm,
+                                   pos=past_kv.pos_t if graph_mode else None)
         elif graph_mode:
             # full-length masked attention over the static cache (constant
             # shapes; unfilled slots are zero + masked by -inf)

@@ -33,6 +33,11 @@ void attn_bwd_into(torch::Tensor dout, torch::Tensor q,
                    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                    int64_t kv_off);
 std::tuple<std::string, int64_t> attn_variant(int64_t S, int64_t D);
+torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                          torch::Tensor slopes, double scale,
+                          c10::optional<torch::Tensor> pos, int64_t n_splits);
+std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t Hkv,
+                                              int64_t Skv, int64_t D);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -118,6 +123,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(S, D) -> (kernel family \"v1\"/\"v2\", waves per workgroup): the "
           "selection table attn_fwd and attn_bwd share; raises on "
           "unsupported shapes");
+    m.def("decode_attn", &decode_attn,
+          "single-query attention over a KV cache: split-KV, in-kernel "
+          "causal + ALiBi + GQA, position read on the device (gfx950)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("slopes"),
+          py::arg("scale"), py::arg("pos") = c10::nullopt,
+          py::arg("n_splits") = 0);
+    m.def("decode_attn_plan", &decode_attn_plan,
+          "(B, Hkv, Skv, D) -> (n_splits, chunk): the auto split-KV plan of "
+          "decode_attn; raises on unsupported shapes");
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,
