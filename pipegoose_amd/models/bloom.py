@@ -174,7 +174,20 @@ class BloomAttention(nn.Module):
         v = fused[..., 2, :].transpose(1, 2)
 
         present = None
-        if past_kv is not None:
+        paged = getattr(past_kv, "paged", False)
+        if paged:
+            # paged cache (models/kv_cache.py PagedKVCache): the new rows go
+            # through the block table at each row's own device position;
+            # k, v stay the fresh rows (a multi-token forward is a prefill
+            # from an empty slot and attends over exactly those)
+            from pipegoose_amd.ops.paged_attention import (
+                paged_decode_attention, paged_kv_write)
+            if S > 1:
+                past_kv.assert_empty()
+            paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
+                           past_kv.block_table, past_kv.pos_t)
+            present = past_kv
+        elif past_kv is not None:
             if hasattr(past_kv, "append"):     # StaticKVCache layer
                 k, v = past_kv.append(k, v)
                 present = past_kv
@@ -191,7 +204,12 @@ class BloomAttention(nn.Module):
             decode_attention, decode_kernel_supported)
         graph_mode = present is not None and getattr(present, "graph_mode",
                                                      False)
-        if (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
+        if paged and S == 1:
+            # one query per row over its pages, per-row position
+            out = paged_decode_attention(
+                q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+        elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
             # single-query decode kernel: the position is the cache's device
             # pos_t in graph mode (read in-kernel), else the last filled slot
             out = decode_attention(q, k, v, self._slopes_f32(q.device),
@@ -435,6 +453,17 @@ class BloomForCausalLM(nn.Module):
         p = next(self.parameters())
         return GraphKVCache(len(self.transformer.h), batch_size,
                             attn.num_heads, max_len, attn.head_dim,
+                            p.dtype, p.device)
+
+    def new_paged_kv_cache(self, max_seqs: int, n_pages: int, page_size: int,
+                           max_len: int):
+        """Paged cache bank: one page pool shared by ``max_seqs`` sequences
+        of up to ``max_len`` tokens each (models/paged_decode.py)."""
+        from pipegoose_amd.models.kv_cache import PagedKVCache
+        attn = self.transformer.h[0].self_attention
+        p = next(self.parameters())
+        return PagedKVCache(len(self.transformer.h), max_seqs, n_pages,
+                            page_size, max_len, attn.num_heads, attn.head_dim,
                             p.dtype, p.device)
 
     def gradient_checkpointing_enable(self, enabled: bool = True):

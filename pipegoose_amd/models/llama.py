@@ -126,7 +126,18 @@ class LlamaAttention(nn.Module):
         v = v.view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
         graph_mode = past_kv is not None and getattr(past_kv, "graph_mode",
                                                      False)
-        if graph_mode:
+        paged = getattr(past_kv, "paged", False)
+        if paged and S == 1:
+            # paged decode: every row sits at its own device position
+            from pipegoose_amd.ops.rope import rope_at_position
+            q = rope_at_position(q, self.rope_theta, past_kv.pos_t)
+            k = rope_at_position(k, self.rope_theta, past_kv.pos_t)
+        elif paged:
+            # a multi-token forward is a prefill from an empty slot
+            past_kv.assert_empty()
+            q = apply_rope(q, self.rope_theta, pos_offset=0)
+            k = apply_rope(k, self.rope_theta, pos_offset=0)
+        elif graph_mode:
             # hipGraph decode: the absolute position is the cache's device
             # pos_t — no host value may enter the captured step
             from pipegoose_amd.ops.rope import rope_at_position
@@ -146,7 +157,16 @@ class LlamaAttention(nn.Module):
             q = apply_rope(q, self.rope_theta, pos_offset=offset)
             k = apply_rope(k, self.rope_theta, pos_offset=offset)
         present = None
-        if past_kv is not None:
+        if paged:
+            # paged cache (models/kv_cache.py PagedKVCache): the new rows go
+            # through the block table at each row's own device position;
+            # k, v stay the fresh rows, which a prefill attends over
+            from pipegoose_amd.ops.paged_attention import (
+                paged_decode_attention, paged_kv_write)
+            paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
+                           past_kv.block_table, past_kv.pos_t)
+            present = past_kv
+        elif past_kv is not None:
             if hasattr(past_kv, "append"):     # StaticKVCache layer
                 k, v = past_kv.append(k, v)
                 present = past_kv
@@ -173,6 +193,11 @@ class LlamaAttention(nn.Module):
                 torch.zeros(self.num_heads, device=q.device),
                 self.inv_norm, parallel_context=self.parallel_context,
                 parallel_mode=ParallelMode.CONTEXT).to(q.dtype)
+        elif paged and S == 1:
+            # one query per row over its pages (GQA mapped in-kernel)
+            out = paged_decode_attention(
+                q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
         elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
             # single-query decode kernel over the un-expanded Hkv-head cache
             # (GQA mapped in-kernel); the position is the cache's device
@@ -368,6 +393,17 @@ class LlamaForCausalLM(nn.Module):
         return GraphKVCache(len(self.model.layers), batch_size,
                             attn.num_kv_heads, max_len, attn.head_dim,
                             p.dtype, p.device)
+
+    def new_paged_kv_cache(self, max_seqs: int, n_pages: int, page_size: int,
+                           max_len: int):
+        """Paged cache bank: one page pool shared by ``max_seqs`` sequences
+        of up to ``max_len`` tokens each (models/paged_decode.py)."""
+        from pipegoose_amd.models.kv_cache import PagedKVCache
+        attn = self.model.layers[0].self_attn
+        p = next(self.parameters())
+        return PagedKVCache(len(self.model.layers), max_seqs, n_pages,
+                            page_size, max_len, attn.num_kv_heads,
+                            attn.head_dim, p.dtype, p.device)
 
     def gradient_checkpointing_enable(self, enabled: bool = True):
         """Recompute each block in backward instead of storing activations —

@@ -38,6 +38,14 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                           c10::optional<torch::Tensor> pos, int64_t n_splits);
 std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t Hkv,
                                               int64_t Skv, int64_t D);
+torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pool,
+                                torch::Tensor v_pool,
+                                torch::Tensor block_table,
+                                torch::Tensor slopes, double scale,
+                                torch::Tensor pos, int64_t n_splits);
+void paged_kv_write(torch::Tensor k_new, torch::Tensor v_new,
+                    torch::Tensor k_pool, torch::Tensor v_pool,
+                    torch::Tensor block_table, torch::Tensor start);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -132,6 +140,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("decode_attn_plan", &decode_attn_plan,
           "(B, Hkv, Skv, D) -> (n_splits, chunk): the auto split-KV plan of "
           "decode_attn; raises on unsupported shapes");
+    m.def("paged_decode_attn", &paged_decode_attn,
+          "decode_attn over a paged cache: pools [n_pages, Hkv, PAGE, D], "
+          "int32 block_table [B, max_pages], page ids clamped in-kernel; the "
+          "plan is decode_attn_plan(B, Hkv, max_pages*PAGE, D) (gfx950)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
+          py::arg("pos"), py::arg("n_splits") = 0);
+    m.def("paged_kv_write", &paged_kv_write,
+          "write new K/V rows [B, Hkv, S_new, D] into the paged pools at "
+          "logical positions start[b] + s (start read on the device); rows "
+          "past max_pages*PAGE are dropped (gfx950)",
+          py::arg("k_new"), py::arg("v_new"), py::arg("k_pool"),
+          py::arg("v_pool"), py::arg("block_table"), py::arg("start"));
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

@@ -45,6 +45,38 @@
 //                         empty and exit at once)
 //
 // decode_attn_plan(B, Hkv, Skv, D) returns the auto (n_splits, chunk).
+//
+// PAGED caches (paged_decode_attn): the same split kernel with PAGED = true.
+// K and V live in pools [n_pages, Hkv, PAGE, D] shared by all sequences, and
+// logical key row j of batch row b is
+//
+//   pool[clamp(block_table[b, j / PAGE], 0, n_pages-1), h/G, j % PAGE, :]
+//
+// with block_table int32 [B, max_pages] (row stride free) and PAGE a power of
+// two in {16, 32, 64, 128}.  Skv := max_pages * PAGE, the plan is make_plan on
+// that, pos is required.  TILE = 64 and NW = 4 give each wave 16 consecutive,
+// 16-aligned rows per tile, and the clamp of a row index to p stays inside
+// them (the wave is only there when its first row is <= p), so for every
+// allowed PAGE the rows a wave loads in one tile sit in ONE page: the table
+// lookup is wave-uniform, one int32 per wave per tile, made uniform with
+// readfirstlane so that it is a scalar load held in an SGPR.  It adds no
+// per-lane load to the K/V address path; the id of the next tile is fetched
+// while the current tile is computed.  "Nothing beyond p is loaded" extends
+// to the table: entries with index > p / PAGE are never read.  Every id that
+// is read is clamped into [0, n_pages-1] before use, so a corrupt table gives
+// wrong numbers and never an out-of-bounds access.  The contiguous
+// instantiations (PAGED = false) compile the address path they always had.
+// The combine kernel is shared as is.
+//
+// paged_kv_write(k_new, v_new, k_pool, v_pool, block_table, start): one
+// launch, one thread per 16-byte packet of a new row, K and V both.  Row s of
+// batch row b ([B, Hkv, S_new, D], any strides with d contiguous) goes to
+// logical position start[b] + s through the table with the same id clamp;
+// `start` (int64, 1 or B elements) is READ ON THE DEVICE, so the call is
+// graph-capturable with the position as data.  For the same reason
+// start + S_new <= max_pages * PAGE cannot be checked on the host: rows whose
+// logical position is < 0 or >= max_pages * PAGE are DROPPED (no wrap, no
+// overrun, no table read).  Nothing but the addressed rows is written.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -128,7 +160,11 @@ __device__ __forceinline__ void merge_state(float& m, float& l, float (&a)[N],
 // GT q heads of the group are processed per pass over the split's keys
 // (GT = 4, 2 or 1, the largest that divides G); G > 4 takes G/GT passes, the
 // later ones reading the chunk from cache.
-template <int D, int GT>
+//
+// PAGED: k and v are the page pools, kb/vb the page strides, and rows are
+// addressed through block_table (file header); otherwise the four paged
+// arguments are unused.
+template <int D, int GT, bool PAGED>
 __global__ __launch_bounds__(NW * WAVE_SIZE)
 void decode_attn_split_kernel(const bf16* __restrict__ q,
                               const bf16* __restrict__ k,
@@ -141,7 +177,9 @@ void decode_attn_split_kernel(const bf16* __restrict__ q,
                               int H, int G, int Skv, int chunk, int n_splits,
                               int64_t qb, int64_t qh,
                               int64_t kb, int64_t kh, int64_t ks,
-                              int64_t vb, int64_t vh, int64_t vs) {
+                              int64_t vb, int64_t vh, int64_t vs,
+                              const int* __restrict__ block_table,
+                              int64_t bt_stride, int n_pages, int page_shift) {
     constexpr int TPR = D / 8;             // lanes per row
     constexpr int RPW = WAVE_SIZE / TPR;   // rows per wave load
     constexpr int RW = TILE / NW;          // rows per wave per tile
@@ -164,8 +202,17 @@ void decode_attn_split_kernel(const bf16* __restrict__ q,
     const int sub = lane % TPR;            // which 8 of the D columns
     const int slot = lane / TPR;           // which row of a wave load
 
-    const bf16* kp = k + b * kb + hk * kh + sub * 8;
-    const bf16* vp = v + b * vb + hk * vh + sub * 8;
+    const bf16* kp = k + (PAGED ? 0 : b * kb) + hk * kh + sub * 8;
+    const bf16* vp = v + (PAGED ? 0 : b * vb) + hk * vh + sub * 8;
+    // PAGED: this wave's rows of a tile are [tile0 + wrow, tile0 + wrow + RW),
+    // inside one page; page_of reads and clamps that page's id (wave-uniform)
+    static_assert(!PAGED || TILE / NW == 16, "a wave's rows must fit a page");
+    const int* bt_row = PAGED ? block_table + b * bt_stride : nullptr;
+    const int wrow = PAGED ? __builtin_amdgcn_readfirstlane(wave * RW) : 0;
+    auto page_of = [&](int row) {
+        const int id = bt_row[__builtin_amdgcn_readfirstlane(row) >> page_shift];
+        return min(max(id, 0), n_pages - 1);
+    };
 
     for (int g0 = 0; g0 < G; g0 += GT) {
         const int h0 = hk * G + g0;
@@ -186,6 +233,9 @@ void decode_attn_split_kernel(const bf16* __restrict__ q,
             l[g] = 0.f;
         }
 
+        int page = 0;
+        if constexpr (PAGED)
+            if (c0 + wrow <= p) page = page_of(c0 + wrow);
         for (int tile0 = c0; tile0 < end; tile0 += TILE) {
             const int rbase = tile0 + wave * RW;
             if (rbase > p) break;          // wave-uniform: whole tile part masked
@@ -194,8 +244,24 @@ void decode_attn_split_kernel(const bf16* __restrict__ q,
             for (int i = 0; i < NL; ++i) {
                 // rows past p are never loaded: the index is clamped to p
                 const int rc = min(rbase + i * RPW + slot, p);
-                kr[i] = *reinterpret_cast<const uint4*>(kp + (int64_t)rc * ks);
-                vr[i] = *reinterpret_cast<const uint4*>(vp + (int64_t)rc * vs);
+                if constexpr (PAGED) {
+                    const int in_page = rc & ((1 << page_shift) - 1);
+                    kr[i] = *reinterpret_cast<const uint4*>(
+                        kp + page * kb + (int64_t)in_page * ks);
+                    vr[i] = *reinterpret_cast<const uint4*>(
+                        vp + page * vb + (int64_t)in_page * vs);
+                } else {
+                    kr[i] = *reinterpret_cast<const uint4*>(
+                        kp + (int64_t)rc * ks);
+                    vr[i] = *reinterpret_cast<const uint4*>(
+                        vp + (int64_t)rc * vs);
+                }
+            }
+            if constexpr (PAGED) {
+                // the next tile's id, only if this wave will be there: table
+                // entries past p / PAGE are never read
+                const int nxt = tile0 + TILE + wrow;
+                if (tile0 + TILE < end && nxt <= p) page = page_of(nxt);
             }
 #pragma unroll
             for (int i = 0; i < NL; ++i) {
@@ -331,63 +397,120 @@ DecodePlan make_plan(int64_t B, int64_t Hkv, int64_t Skv, int64_t D,
 
 // a bf16 4-d device tensor of the given sizes whose rows the kernel can read
 // as 16-byte packets
-void check_operand(const char* name, const torch::Tensor& t,
+void check_operand(const char* op, const char* name, const torch::Tensor& t,
                    torch::IntArrayRef sizes) {
-    TORCH_CHECK(t.is_cuda(), "decode_attn: ", name, " must be on the GPU");
-    TORCH_CHECK(t.scalar_type() == torch::kBFloat16, "decode_attn: ", name,
+    TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+    TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": ", name,
                 " must be bf16");
-    TORCH_CHECK(t.sizes() == sizes, "decode_attn: ", name, " has sizes ",
+    TORCH_CHECK(t.sizes() == sizes, op, ": ", name, " has sizes ",
                 t.sizes(), ", expected ", sizes);
-    TORCH_CHECK(t.stride(3) == 1, "decode_attn: last dim of ", name,
+    TORCH_CHECK(t.stride(3) == 1, op, ": last dim of ", name,
                 " must be contiguous");
     for (int i = 0; i < 3; ++i)
-        TORCH_CHECK(t.size(i) == 1 || t.stride(i) % 8 == 0, "decode_attn: ",
+        TORCH_CHECK(t.size(i) == 1 || t.stride(i) % 8 == 0, op, ": ",
                     name, " stride ", i, " must be a multiple of 8 elements");
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-                "decode_attn: ", name, " must be 16-byte aligned");
+                op, ": ", name, " must be 16-byte aligned");
 }
 
-}  // namespace
-
-std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t Hkv,
-                                              int64_t Skv, int64_t D) {
-    const DecodePlan plan = make_plan(B, Hkv, Skv, D, 0);
-    return {plan.n_splits, plan.chunk};
+// an int64 device tensor of 1 or B elements that a kernel reads as the
+// position (decode) or the first position to write (paged_kv_write)
+void check_position(const char* op, const char* name, const torch::Tensor& t,
+                    int64_t B) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kLong &&
+                t.is_contiguous() && (t.numel() == 1 || t.numel() == B),
+                op, ": ", name, " must be a contiguous int64 GPU tensor "
+                "with 1 or ", B, " elements");
 }
 
-torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                          torch::Tensor slopes, double scale,
-                          c10::optional<torch::Tensor> pos, int64_t n_splits) {
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
-                "decode_attn: q must be [B, H, 1, D], k and v [B, Hkv, Skv, D]");
+// The two pools [n_pages, Hkv, PAGE, D] and the table [B, max_pages] of the
+// paged ops; returns log2(PAGE).
+int check_paged(const char* op, const torch::Tensor& k_pool,
+                const torch::Tensor& v_pool, const torch::Tensor& block_table,
+                int64_t B, int64_t D, const torch::Device& device) {
+    TORCH_CHECK(k_pool.dim() == 4 && v_pool.dim() == 4, op,
+                ": k_pool and v_pool must be [n_pages, Hkv, PAGE, D]");
+    const int64_t n_pages = k_pool.size(0), Hkv = k_pool.size(1);
+    const int64_t page = k_pool.size(2);
+    TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, op,
+                ": page size must be 16, 32, 64 or 128, got ", page);
+    TORCH_CHECK(D == 64 || D == 128, op,
+                ": head dim must be 64 or 128, got ", D);
+    check_operand(op, "k_pool", k_pool, {n_pages, Hkv, page, D});
+    check_operand(op, "v_pool", v_pool, {n_pages, Hkv, page, D});
+    TORCH_CHECK(n_pages > 0 && n_pages < (int64_t)1 << 31 && Hkv > 0, op,
+                ": the pools must hold at least one page and one head");
+    TORCH_CHECK(block_table.is_cuda() &&
+                block_table.scalar_type() == torch::kInt, op,
+                ": block_table must be an int32 GPU tensor");
+    TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+                block_table.size(1) > 0 &&
+                (block_table.stride(1) == 1 || block_table.size(1) == 1), op,
+                ": block_table must be [", B, ", max_pages] with contiguous "
+                "rows, got sizes ", block_table.sizes());
+    TORCH_CHECK(block_table.size(1) * page < (int64_t)1 << 30, op,
+                ": max_pages * PAGE too large");
+    TORCH_CHECK(k_pool.device() == device && v_pool.device() == device &&
+                block_table.device() == device, op,
+                ": all operands must be on the same device");
+    int shift = 4;
+    while ((1 << shift) < page) ++shift;
+    return shift;
+}
+
+// One thread per 16-byte packet of a new row; K and V in the same launch.
+// Rows whose logical position falls outside [0, capacity) are dropped.
+template <int D>
+__global__ __launch_bounds__(256)
+void paged_kv_write_kernel(const bf16* __restrict__ k_new,
+                           const bf16* __restrict__ v_new,
+                           bf16* __restrict__ k_pool,
+                           bf16* __restrict__ v_pool,
+                           const int* __restrict__ block_table,
+                           int64_t bt_stride,
+                           const int64_t* __restrict__ start, int start_n,
+                           int64_t total, int Hkv, int S_new, int capacity,
+                           int n_pages, int page_shift,
+                           int64_t knb, int64_t knh, int64_t kns,
+                           int64_t vnb, int64_t vnh, int64_t vns,
+                           int64_t kpp, int64_t kph, int64_t kps,
+                           int64_t vpp, int64_t vph, int64_t vps) {
+    constexpr int TPR = D / 8;
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int sub = (int)(idx % TPR);
+    int64_t rest = idx / TPR;
+    const int hk = (int)(rest % Hkv);      // heads innermost: the models'
+    rest /= Hkv;                           // views are [B, S, Hkv, D] in memory
+    const int s = (int)(rest % S_new);
+    const int b = (int)(rest / S_new);
+    const int64_t row = start[start_n == 1 ? 0 : b] + s;
+    if (row < 0 || row >= capacity) return;
+    const int r = (int)row;
+    int page = block_table[b * bt_stride + (r >> page_shift)];
+    page = min(max(page, 0), n_pages - 1);
+    const int in_page = r & ((1 << page_shift) - 1);
+    const uint4 kv = *reinterpret_cast<const uint4*>(
+        k_new + b * knb + hk * knh + s * kns + sub * 8);
+    const uint4 vv = *reinterpret_cast<const uint4*>(
+        v_new + b * vnb + hk * vnh + s * vns + sub * 8);
+    *reinterpret_cast<uint4*>(
+        k_pool + page * kpp + hk * kph + in_page * kps + sub * 8) = kv;
+    *reinterpret_cast<uint4*>(
+        v_pool + page * vpp + hk * vph + in_page * vps + sub * 8) = vv;
+}
+
+// The two launches behind decode_attn and paged_decode_attn.  PAGED: k and v
+// are the pools and Skv = max_pages * PAGE.
+template <bool PAGED>
+torch::Tensor launch_decode(const torch::Tensor& q, const torch::Tensor& k,
+                            const torch::Tensor& v,
+                            const torch::Tensor& slopes, double scale,
+                            const int64_t* pos_ptr, int pos_n,
+                            const DecodePlan& plan, int64_t Hkv, int64_t Skv,
+                            const int* bt_ptr, int64_t bt_stride, int n_pages,
+                            int page_shift) {
     const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
-    const int64_t Hkv = k.size(1), Skv = k.size(2);
-    check_operand("q", q, {B, H, 1, D});
-    check_operand("k", k, {B, Hkv, Skv, D});
-    check_operand("v", v, {B, Hkv, Skv, D});
-    TORCH_CHECK(Hkv > 0 && H % Hkv == 0,
-                "decode_attn: q heads must be a multiple of kv heads");
-    TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
-                "decode_attn: q, k and v must be on the same device");
-    TORCH_CHECK(slopes.is_cuda() && slopes.scalar_type() == torch::kFloat &&
-                slopes.numel() == H && slopes.is_contiguous(),
-                "decode_attn: slopes must be ", H,
-                " contiguous fp32 values on the GPU");
-    const int64_t* pos_ptr = nullptr;
-    int pos_n = 0;
-    if (pos.has_value()) {
-        const torch::Tensor& pt = *pos;
-        TORCH_CHECK(pt.is_cuda() && pt.scalar_type() == torch::kLong &&
-                    pt.is_contiguous() &&
-                    (pt.numel() == 1 || pt.numel() == B),
-                    "decode_attn: pos must be a contiguous int64 GPU tensor "
-                    "with 1 or ", B, " elements");
-        pos_ptr = pt.data_ptr<int64_t>();
-        pos_n = (int)pt.numel();
-    }
-    const DecodePlan plan = make_plan(B, Hkv, Skv, D, n_splits);
-    TORCH_CHECK(Hkv <= 65535 && B <= 65535 && H <= 65535,
-                "decode_attn: B, H and Hkv must fit a grid dimension");
     const int G = (int)(H / Hkv);
 
     // physically [B, 1, H, D]: the model's reshape to [B, 1, H*D] is free
@@ -399,7 +522,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     auto stream = at::cuda::getCurrentCUDAStream();
     auto launch_split = [&](auto dv_, auto gt_) {
         constexpr int DV = decltype(dv_)::value, GT = decltype(gt_)::value;
-        hipLaunchKernelGGL((decode_attn_split_kernel<DV, GT>),
+        hipLaunchKernelGGL((decode_attn_split_kernel<DV, GT, PAGED>),
                            dim3(plan.n_splits, Hkv, B), dim3(NW * WAVE_SIZE),
                            0, stream,
                            reinterpret_cast<const bf16*>(q.data_ptr()),
@@ -411,7 +534,8 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                            plan.chunk, plan.n_splits,
                            q.stride(0), q.stride(1),
                            k.stride(0), k.stride(1), k.stride(2),
-                           v.stride(0), v.stride(1), v.stride(2));
+                           v.stride(0), v.stride(1), v.stride(2),
+                           bt_ptr, bt_stride, n_pages, page_shift);
     };
     auto with_gt = [&](auto dv_) {
         if (G % 4 == 0) launch_split(dv_, std::integral_constant<int, 4>{});
@@ -435,4 +559,122 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     else launch_combine(std::integral_constant<int, 128>{});
     HIP_CHECK_LAUNCH();
     return o_phys.permute({0, 2, 1, 3});
+}
+
+}  // namespace
+
+std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t Hkv,
+                                              int64_t Skv, int64_t D) {
+    const DecodePlan plan = make_plan(B, Hkv, Skv, D, 0);
+    return {plan.n_splits, plan.chunk};
+}
+
+
+torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                          torch::Tensor slopes, double scale,
+                          c10::optional<torch::Tensor> pos, int64_t n_splits) {
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+                "decode_attn: q must be [B, H, 1, D], k and v [B, Hkv, Skv, D]");
+    const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
+    const int64_t Hkv = k.size(1), Skv = k.size(2);
+    check_operand("decode_attn", "q", q, {B, H, 1, D});
+    check_operand("decode_attn", "k", k, {B, Hkv, Skv, D});
+    check_operand("decode_attn", "v", v, {B, Hkv, Skv, D});
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0,
+                "decode_attn: q heads must be a multiple of kv heads");
+    TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+                "decode_attn: q, k and v must be on the same device");
+    TORCH_CHECK(slopes.is_cuda() && slopes.scalar_type() == torch::kFloat &&
+                slopes.numel() == H && slopes.is_contiguous(),
+                "decode_attn: slopes must be ", H,
+                " contiguous fp32 values on the GPU");
+    const int64_t* pos_ptr = nullptr;
+    int pos_n = 0;
+    if (pos.has_value()) {
+        check_position("decode_attn", "pos", *pos, B);
+        pos_ptr = pos->data_ptr<int64_t>();
+        pos_n = (int)pos->numel();
+    }
+    const DecodePlan plan = make_plan(B, Hkv, Skv, D, n_splits);
+    TORCH_CHECK(Hkv <= 65535 && B <= 65535 && H <= 65535,
+                "decode_attn: B, H and Hkv must fit a grid dimension");
+    return launch_decode<false>(q, k, v, slopes, scale, pos_ptr, pos_n, plan,
+                                Hkv, Skv, nullptr, 0, 0, 0);
+}
+
+torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pool,
+                                torch::Tensor v_pool,
+                                torch::Tensor block_table,
+                                torch::Tensor slopes, double scale,
+                                torch::Tensor pos, int64_t n_splits) {
+    const char* op = "paged_decode_attn";
+    TORCH_CHECK(q.dim() == 4, op, ": q must be [B, H, 1, D]");
+    const int64_t B = q.size(0), H = q.size(1), D = q.size(3);
+    check_operand(op, "q", q, {B, H, 1, D});
+    const int shift = check_paged(op, k_pool, v_pool, block_table, B, D,
+                                  q.device());
+    const int64_t n_pages = k_pool.size(0), Hkv = k_pool.size(1);
+    const int64_t Skv = block_table.size(1) << shift;
+    TORCH_CHECK(H % Hkv == 0, op,
+                ": q heads must be a multiple of kv heads");
+    TORCH_CHECK(slopes.is_cuda() && slopes.scalar_type() == torch::kFloat &&
+                slopes.numel() == H && slopes.is_contiguous(), op,
+                ": slopes must be ", H, " contiguous fp32 values on the GPU");
+    check_position(op, "pos", pos, B);
+    const DecodePlan plan = make_plan(B, Hkv, Skv, D, n_splits);
+    TORCH_CHECK(Hkv <= 65535 && B <= 65535 && H <= 65535, op,
+                ": B, H and Hkv must fit a grid dimension");
+    return launch_decode<true>(q, k_pool, v_pool, slopes, scale,
+                               pos.data_ptr<int64_t>(), (int)pos.numel(),
+                               plan, Hkv, Skv, block_table.data_ptr<int>(),
+                               block_table.stride(0), (int)n_pages, shift);
+}
+
+void paged_kv_write(torch::Tensor k_new, torch::Tensor v_new,
+                    torch::Tensor k_pool, torch::Tensor v_pool,
+                    torch::Tensor block_table, torch::Tensor start) {
+    const char* op = "paged_kv_write";
+    TORCH_CHECK(k_new.dim() == 4 && v_new.dim() == 4, op,
+                ": k_new and v_new must be [B, Hkv, S_new, D]");
+    const int64_t B = k_new.size(0), Hkv = k_new.size(1);
+    const int64_t S_new = k_new.size(2), D = k_new.size(3);
+    check_operand(op, "k_new", k_new, {B, Hkv, S_new, D});
+    check_operand(op, "v_new", v_new, {B, Hkv, S_new, D});
+    const int shift = check_paged(op, k_pool, v_pool, block_table, B, D,
+                                  k_new.device());
+    TORCH_CHECK(v_new.device() == k_new.device(), op,
+                ": all operands must be on the same device");
+    TORCH_CHECK(k_pool.size(1) == Hkv, op, ": the pools have ",
+                k_pool.size(1), " kv heads, the new rows ", Hkv);
+    check_position(op, "start", start, B);
+    TORCH_CHECK(S_new < (int64_t)1 << 30 && Hkv <= 65535, op,
+                ": S_new or Hkv too large");
+    const int64_t total = B * Hkv * S_new * (D / 8);
+    if (total == 0) return;
+    const int64_t capacity = block_table.size(1) << shift;
+    constexpr int THREADS = 256;
+    const int64_t blocks = (total + THREADS - 1) / THREADS;
+    TORCH_CHECK(blocks < (int64_t)1 << 31, op, ": too many rows for one launch");
+
+    auto stream = at::cuda::getCurrentCUDAStream();
+    auto launch = [&](auto dv_) {
+        constexpr int DV = decltype(dv_)::value;
+        hipLaunchKernelGGL((paged_kv_write_kernel<DV>), dim3((unsigned)blocks),
+                           dim3(THREADS), 0, stream,
+                           reinterpret_cast<const bf16*>(k_new.data_ptr()),
+                           reinterpret_cast<const bf16*>(v_new.data_ptr()),
+                           reinterpret_cast<bf16*>(k_pool.data_ptr()),
+                           reinterpret_cast<bf16*>(v_pool.data_ptr()),
+                           block_table.data_ptr<int>(), block_table.stride(0),
+                           start.data_ptr<int64_t>(), (int)start.numel(),
+                           total, (int)Hkv, (int)S_new, (int)capacity,
+                           (int)k_pool.size(0), shift,
+                           k_new.stride(0), k_new.stride(1), k_new.stride(2),
+                           v_new.stride(0), v_new.stride(1), v_new.stride(2),
+                           k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                           v_pool.stride(0), v_pool.stride(1), v_pool.stride(2));
+    };
+    if (D == 64) launch(std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 128>{});
+    HIP_CHECK_LAUNCH();
 }

@@ -54,14 +54,17 @@ def apply_rope(x: torch.Tensor, theta_base: float = 10000.0,
 
 def rope_at_position(x: torch.Tensor, theta_base: float,
                      pos_t: torch.Tensor) -> torch.Tensor:
-    """x: [B, H, 1, D], pos_t: int64 device tensor [1] — rotate the single
-    decode step at a DATA-carried position (hipGraph-capturable: no host
-    value enters; same half-split math as _rope_ref)."""
+    """x: [B, H, 1, D], pos_t: int64 device tensor [1], or [B] for one
+    position per batch row (ragged batches over a paged cache) — rotate the
+    single decode step at a DATA-carried position (hipGraph-capturable: no
+    host value enters; same half-split math as _rope_ref)."""
     half = x.size(-1) // 2
     d = torch.arange(half, device=x.device, dtype=torch.float32)
     freqs = theta_base ** (-2.0 * d / x.size(-1))
-    ang = pos_t.float()[:, None] * freqs          # [1, half]
+    ang = pos_t.float()[:, None] * freqs          # [1 or B, half]
     cos, sin = ang.cos(), ang.sin()
+    if pos_t.numel() > 1:                         # per row: [B, 1, 1, half]
+        cos, sin = cos[:, None, None, :], sin[:, None, None, :]
     x1, x2 = x[..., :half].float(), x[..., half:].float()
     y1 = x1 * cos - x2 * sin
     y2 = x2 * cos + x1 * sin
