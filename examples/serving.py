@@ -66,6 +66,28 @@ def main():
         mode = "hipGraph" if dec._graph is not None else "eager"
         print(f"graph decoder ({mode}): {args.batch * out2.size(1) / dt_g:,.0f} "
               f"tokens/s incl. prefill")
+
+        # ragged prompts over a paged cache: a shared system prompt keeps its
+        # whole pages once (share_prefix), and long prompts go in pieces
+        # (prefill_chunk) — models/paged_decode.py
+        from pipegoose_amd.models.paged_decode import PagedDecoder
+        system = ids[0, :args.prompt_len // 2]
+        prompts = [torch.cat([system, ids[i, :8 + 5 * i]])
+                   for i in range(min(args.batch, 4))]
+        longest = max(p.numel() for p in prompts) + args.new_tokens
+        paged = PagedDecoder(model, max_seqs=len(prompts),
+                             n_pages=len(prompts) * (longest // 16 + 1) + 1,
+                             max_len=longest,
+                             prefill_chunk=max(16, args.prompt_len // 4))
+        t0 = time.perf_counter()
+        outs = paged.generate(prompts, max_new_tokens=args.new_tokens,
+                              share_prefix=True)
+        if dev == "cuda":
+            torch.cuda.synchronize()
+        dt_p = time.perf_counter() - t0
+        print(f"paged decoder, {len(prompts)} ragged prompts sharing "
+              f"{system.numel()} tokens: {sum(o.numel() for o in outs)} new "
+              f"tokens in {dt_p * 1e3:.1f} ms")
     ctx.destroy()
 
 

@@ -177,13 +177,14 @@ class BloomAttention(nn.Module):
         paged = getattr(past_kv, "paged", False)
         if paged:
             # paged cache (models/kv_cache.py PagedKVCache): the new rows go
-            # through the block table at each row's own device position;
-            # k, v stay the fresh rows (a multi-token forward is a prefill
-            # from an empty slot and attends over exactly those)
+            # through the block table at each row's own device position.
+            # A multi-token forward into empty slots attends over exactly
+            # its fresh rows k, v; behind a cached prefix (chunked prefill,
+            # prefix reuse) it attends over the pools
             from pipegoose_amd.ops.paged_attention import (
-                paged_decode_attention, paged_kv_write)
-            if S > 1:
-                past_kv.assert_empty()
+                paged_decode_attention, paged_kv_write,
+                paged_prefill_attention)
+            paged_prefix = S > 1 and past_kv.has_prefix(S)
             paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
                            past_kv.block_table, past_kv.pos_t)
             present = past_kv
@@ -207,6 +208,12 @@ class BloomAttention(nn.Module):
         if paged and S == 1:
             # one query per row over its pages, per-row position
             out = paged_decode_attention(
+                q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+        elif paged and paged_prefix:
+            # S query rows at pos_t .. pos_t+S-1 over the pages, which hold
+            # the prefix and (just written) the chunk itself
+            out = paged_prefill_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
                 self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
         elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):

@@ -136,9 +136,15 @@ class PagedLayerView:
         self._rows = rows
 
     def assert_empty(self):
-        """Multi-token forwards are prefills from empty slots only (no
-        prefix reuse, no chunked prefill); checked on the host mirror."""
+        """Raise unless every slot of the range is empty (host mirror)."""
         self._rows.assert_empty()
+
+    def has_prefix(self, n_new: int = 0) -> bool:
+        """Whether any slot of the range already holds tokens (host mirror):
+        a multi-token forward then attends over the pools behind ``pos_t``
+        (chunked prefill, prefix reuse) instead of over its fresh rows, and
+        its ``n_new`` tokens must fit the pages every slot has."""
+        return self._rows.has_prefix(n_new)
 
 
 class PagedRows:
@@ -163,6 +169,21 @@ class PagedRows:
         assert not any(filled), (
             f"paged prefill needs empty slots, slots {self.lo}..{self.hi - 1} "
             f"hold {filled} tokens")
+
+    def has_prefix(self, n_new: int = 0) -> bool:
+        cache = self.cache
+        if not any(cache.filled[self.lo:self.hi]):
+            return False
+        # rows written past a slot's pages would land in the null page and
+        # be read back as if they were the sequence
+        for slot in range(self.lo, self.hi):
+            room = len(cache.pages[slot]) * cache.page_size
+            assert cache.filled[slot] + n_new <= room, (
+                f"paged prefill of {n_new} tokens runs past the pages of "
+                f"slot {slot} ({cache.filled[slot]} tokens held, pages for "
+                f"{room}): allocate() first, or free() the slot and prefill "
+                f"it empty")
+        return True
 
     def advance(self, n: int = 1):
         """The forward just run wrote ``n`` tokens per row: move the device
@@ -192,8 +213,12 @@ class PagedKVCache:
 
     Page 0 is a reserved null page: it is never handed out and the table is
     initialised to 0, so a stale entry can only ever name the null page.
-    Pages are handed out from a host free list; no page is ever owned by two
-    slots, and running out raises before anything is launched."""
+    Pages are handed out from a host free list with a per-page reference
+    count, and running out raises before anything is launched.  A page is
+    held by two slots only through ``fork``, which shares WHOLE pages of a
+    prefix: a shared page is full and lies below ``filled`` of every holder,
+    so nobody ever writes it and no copy-on-write is needed.  Every other
+    page has exactly one holder."""
 
     def __init__(self, n_layers: int, max_seqs: int, n_pages: int,
                  page_size: int, max_len: int, Hkv: int, D: int,
@@ -219,6 +244,7 @@ class PagedKVCache:
         self.filled: List[int] = [0] * max_seqs        # host mirror of pos_t
         self.pages: List[List[int]] = [[] for _ in range(max_seqs)]
         self._free: List[int] = list(range(n_pages - 1, 0, -1))
+        self.refcount: List[int] = [0] * n_pages
 
     @property
     def n_free_pages(self) -> int:
@@ -242,18 +268,46 @@ class PagedKVCache:
                 f"{self.n_pages - 1} are free")
         for _ in range(need):
             page = self._free.pop()
+            self.refcount[page] = 1
             self.table_host[slot, len(self.pages[slot])] = page
             self.pages[slot].append(page)
         self.block_table[slot].copy_(self.table_host[slot])
 
     def free(self, slot: int):
-        """Return the slot's pages; zero its table row and position."""
-        self._free.extend(reversed(self.pages[slot]))
+        """Drop the slot's hold on its pages, returning those nobody else
+        holds; zero its table row and position."""
+        for page in reversed(self.pages[slot]):
+            self.refcount[page] -= 1
+            if self.refcount[page] == 0:
+                self._free.append(page)
         self.pages[slot] = []
         self.table_host[slot].zero_()
         self.block_table[slot].zero_()
         self.pos_t[slot] = 0
         self.filled[slot] = 0
+
+    def fork(self, src: int, dst: int, n_tokens: int) -> int:
+        """Share the first ``n_tokens // page_size`` WHOLE pages of ``src``
+        with the empty slot ``dst`` and set ``dst``'s table row, position and
+        ``filled`` to the shared token count, which is returned.  ``allocate``
+        then appends fresh pages after the shared ones."""
+        assert src != dst, "fork needs two different slots"
+        assert self.filled[dst] == 0 and not self.pages[dst], (
+            f"fork needs an empty slot that owns no pages, slot {dst} holds "
+            f"{self.filled[dst]} tokens on {len(self.pages[dst])} pages")
+        assert 0 <= n_tokens <= self.filled[src], (
+            f"fork of {n_tokens} tokens, slot {src} holds {self.filled[src]}")
+        n_shared = n_tokens // self.page_size
+        shared = self.pages[src][:n_shared]
+        for i, page in enumerate(shared):
+            self.refcount[page] += 1
+            self.table_host[dst, i] = page
+        self.pages[dst] = list(shared)
+        tokens = n_shared * self.page_size
+        self.block_table[dst].copy_(self.table_host[dst])
+        self.pos_t[dst] = tokens
+        self.filled[dst] = tokens
+        return tokens
 
     def rows(self, lo: int, hi: int) -> PagedRows:
         return PagedRows(self, lo, hi)

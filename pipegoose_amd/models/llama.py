@@ -127,14 +127,15 @@ class LlamaAttention(nn.Module):
         graph_mode = past_kv is not None and getattr(past_kv, "graph_mode",
                                                      False)
         paged = getattr(past_kv, "paged", False)
-        if paged and S == 1:
-            # paged decode: every row sits at its own device position
+        paged_prefix = paged and S > 1 and past_kv.has_prefix(S)
+        if paged and (S == 1 or paged_prefix):
+            # paged decode, or a prefill chunk behind a cached prefix: row i
+            # sits at its sequence's own device position + i
             from pipegoose_amd.ops.rope import rope_at_position
             q = rope_at_position(q, self.rope_theta, past_kv.pos_t)
             k = rope_at_position(k, self.rope_theta, past_kv.pos_t)
         elif paged:
-            # a multi-token forward is a prefill from an empty slot
-            past_kv.assert_empty()
+            # a multi-token forward into empty slots starts at position 0
             q = apply_rope(q, self.rope_theta, pos_offset=0)
             k = apply_rope(k, self.rope_theta, pos_offset=0)
         elif graph_mode:
@@ -160,9 +161,11 @@ class LlamaAttention(nn.Module):
         if paged:
             # paged cache (models/kv_cache.py PagedKVCache): the new rows go
             # through the block table at each row's own device position;
-            # k, v stay the fresh rows, which a prefill attends over
+            # k, v stay the fresh rows, which a prefill into empty slots
+            # attends over
             from pipegoose_amd.ops.paged_attention import (
-                paged_decode_attention, paged_kv_write)
+                paged_decode_attention, paged_kv_write,
+                paged_prefill_attention)
             paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
                            past_kv.block_table, past_kv.pos_t)
             present = past_kv
@@ -196,6 +199,12 @@ class LlamaAttention(nn.Module):
         elif paged and S == 1:
             # one query per row over its pages (GQA mapped in-kernel)
             out = paged_decode_attention(
+                q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+        elif paged_prefix:
+            # S query rows at pos_t .. pos_t+S-1 over the pages, which hold
+            # the prefix and (just written) the chunk itself
+            out = paged_prefill_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
                 self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
         elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):

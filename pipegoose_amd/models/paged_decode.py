@@ -14,6 +14,13 @@ exactly as ``GraphDecoder._capture`` does, keyed by the number of live rows;
 CPU, ``use_graph=False`` or a failed capture step eagerly with identical
 numerics.  Greedy, tp=1.
 
+``prefill_chunk`` feeds a prompt in pieces of at most that many tokens (the
+later pieces attend over the pages behind them: paged prefill attention,
+csrc/paged_prefill_attention.hip), which bounds the activation memory and the
+latency of one forward.  ``share_prefix`` lets a prompt reuse the whole pages
+of the longest token prefix it has in common with an earlier prompt of the
+same call (``PagedKVCache.fork``) and prefills only the rest.
+
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """
 from typing import List, Optional
@@ -33,11 +40,15 @@ class PagedDecoder:
 
     ``prompts`` is a list of up to ``max_seqs`` 1-D long tensors of any
     lengths; ``outs[i]`` holds the ``max_new_tokens`` tokens after
-    ``prompts[i]``.  ``n_pages`` counts the reserved null page 0."""
+    ``prompts[i]``.  ``n_pages`` counts the reserved null page 0.
+    ``prefill_chunk=None`` prefills every prompt in one forward."""
 
     def __init__(self, model, max_seqs: int, n_pages: int,
                  page_size: int = DEFAULT_PAGE_SIZE, max_len: int = 2048,
-                 use_graph: Optional[bool] = None):
+                 use_graph: Optional[bool] = None,
+                 prefill_chunk: Optional[int] = None):
+        assert prefill_chunk is None or prefill_chunk >= 1
+        self.prefill_chunk = prefill_chunk
         ctx = getattr(model, "parallel_context", None)
         if ctx is not None and ctx.get_world_size(ParallelMode.TENSOR) > 1:
             raise NotImplementedError(
@@ -102,28 +113,80 @@ class PagedDecoder:
 
     # -------------------------------------------------------------- generate
 
+    def _shared_prefixes(self, prompts: List[torch.Tensor]):
+        """For every prompt, (earlier prompt, shared tokens): the longest
+        common token prefix with an earlier prompt, rounded down to whole
+        pages and capped at ``len - 1`` so that at least one token is run;
+        (None, 0) where nothing is shared.  Compared on the host."""
+        page = self.cache.page_size
+        host = [p.tolist() for p in prompts]
+        plan = []
+        for i, tokens in enumerate(host):
+            best_src, best = None, 0
+            for j in range(i):
+                other = host[j]
+                common = 0
+                limit = min(len(tokens) - 1, len(other))
+                while common < limit and tokens[common] == other[common]:
+                    common += 1
+                common = common // page * page
+                if common > best:
+                    best_src, best = j, common
+            plan.append((best_src, best))
+        return plan
+
     @torch.no_grad()
-    def generate(self, prompts: List[torch.Tensor], max_new_tokens: int
-                 ) -> List[torch.Tensor]:
+    def _prefill(self, slot: int, prompt: torch.Tensor, done: int = 0):
+        """Run tokens ``done..`` of ``prompt`` into ``slot`` (which holds the
+        first ``done``), whole or in pieces of ``prefill_chunk``; leaves the
+        first new token in ``ids[slot]``."""
+        rows = self.cache.rows(slot, slot + 1)
+        prompt = prompt.to(self.device)
+        step = self.prefill_chunk or prompt.numel()
+        logits = None
+        for lo in range(done, prompt.numel(), step):
+            piece = prompt[lo:lo + step]
+            logits, _ = self.model(piece[None], past=rows, use_cache=True)
+            rows.advance(piece.numel())
+        self.ids[slot].copy_(logits[0, -1].argmax(-1, keepdim=True))
+
+    @torch.no_grad()
+    def generate(self, prompts: List[torch.Tensor], max_new_tokens: int,
+                 share_prefix: bool = False) -> List[torch.Tensor]:
         n = len(prompts)
         cache = self.cache
         assert 1 <= n <= cache.max_seqs, "more prompts than max_seqs"
         assert max_new_tokens >= 1
         self.model.eval()
         try:
-            # every page the run needs, before anything is launched: running
-            # out raises here, and the decode steps have static addresses
-            for i, prompt in enumerate(prompts):
+            for prompt in prompts:
                 assert prompt.dim() == 1 and prompt.numel() >= 1
-                cache.allocate(i, prompt.numel() + max_new_tokens)
+            shared = self._shared_prefixes(prompts) if share_prefix \
+                else [(None, 0)] * n
+            # every page the run needs (shared pages count once), before
+            # anything is launched: running out raises here, and the decode
+            # steps have static addresses
+            page = cache.page_size
+            longest = max(p.numel() for p in prompts) + max_new_tokens
+            if longest > cache.max_len:
+                raise RuntimeError(
+                    f"PagedKVCache: {longest} tokens exceed max_len "
+                    f"{cache.max_len}")
+            fresh = sum(-(-(p.numel() + max_new_tokens) // page) - sh // page
+                        for p, (_, sh) in zip(prompts, shared))
+            if fresh > cache.n_free_pages:
+                raise RuntimeError(
+                    f"PagedKVCache: out of pages: the run needs {fresh}, "
+                    f"{cache.n_free_pages} of {cache.n_pages - 1} are free")
 
-            # prefill each prompt alone into its slot
+            # prefill each prompt alone into its slot, behind the pages it
+            # shares with an earlier one
             for i, prompt in enumerate(prompts):
-                rows = cache.rows(i, i + 1)
-                logits, _ = self.model(prompt.to(self.device)[None],
-                                       past=rows, use_cache=True)
-                self.ids[i].copy_(logits[0, -1].argmax(-1, keepdim=True))
-                rows.advance(prompt.numel())
+                src, sh = shared[i]
+                if sh:
+                    cache.fork(src, i, sh)
+                cache.allocate(i, prompt.numel() + max_new_tokens)
+                self._prefill(i, prompt, done=sh)
 
             tokens = [self.ids[:n].clone()]
             remaining = max_new_tokens - 1

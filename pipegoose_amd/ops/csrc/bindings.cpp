@@ -46,6 +46,11 @@ torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pool,
 void paged_kv_write(torch::Tensor k_new, torch::Tensor v_new,
                     torch::Tensor k_pool, torch::Tensor v_pool,
                     torch::Tensor block_table, torch::Tensor start);
+torch::Tensor paged_prefill_attn(torch::Tensor q, torch::Tensor k_pool,
+                                 torch::Tensor v_pool,
+                                 torch::Tensor block_table,
+                                 torch::Tensor slopes, double scale,
+                                 torch::Tensor start);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -153,6 +158,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "past max_pages*PAGE are dropped (gfx950)",
           py::arg("k_new"), py::arg("v_new"), py::arg("k_pool"),
           py::arg("v_pool"), py::arg("block_table"), py::arg("start"));
+    m.def("paged_prefill_attn", &paged_prefill_attn,
+          "causal attention of Sq >= 1 query rows at positions start[b] + i "
+          "over a paged cache (chunked prefill, prefix reuse): start read on "
+          "the device, page ids clamped in-kernel, rows outside "
+          "[0, max_pages*PAGE) give zeros (gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
+          py::arg("start"));
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

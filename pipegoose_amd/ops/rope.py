@@ -54,17 +54,24 @@ def apply_rope(x: torch.Tensor, theta_base: float = 10000.0,
 
 def rope_at_position(x: torch.Tensor, theta_base: float,
                      pos_t: torch.Tensor) -> torch.Tensor:
-    """x: [B, H, 1, D], pos_t: int64 device tensor [1], or [B] for one
-    position per batch row (ragged batches over a paged cache) — rotate the
-    single decode step at a DATA-carried position (hipGraph-capturable: no
-    host value enters; same half-split math as _rope_ref)."""
+    """x: [B, H, S, D], pos_t: int64 device tensor [1], or [B] for one
+    position per batch row (ragged batches over a paged cache) — rotate row
+    ``i`` at the DATA-carried position ``pos_t[b] + i`` (hipGraph-capturable:
+    no host value enters; same half-split math as _rope_ref).  ``S == 1`` is
+    the decode step, ``S > 1`` a prefill chunk behind a cached prefix."""
     half = x.size(-1) // 2
+    S = x.size(2)
     d = torch.arange(half, device=x.device, dtype=torch.float32)
     freqs = theta_base ** (-2.0 * d / x.size(-1))
-    ang = pos_t.float()[:, None] * freqs          # [1 or B, half]
-    cos, sin = ang.cos(), ang.sin()
-    if pos_t.numel() > 1:                         # per row: [B, 1, 1, half]
-        cos, sin = cos[:, None, None, :], sin[:, None, None, :]
+    if S == 1:
+        ang = pos_t.float()[:, None] * freqs          # [1 or B, half]
+        cos, sin = ang.cos(), ang.sin()
+        if pos_t.numel() > 1:                         # per row: [B, 1, 1, half]
+            cos, sin = cos[:, None, None, :], sin[:, None, None, :]
+    else:
+        pos = pos_t[:, None] + torch.arange(S, device=x.device)
+        ang = pos.float()[:, :, None] * freqs         # [1 or B, S, half]
+        cos, sin = ang.cos()[:, None], ang.sin()[:, None]
     x1, x2 = x[..., :half].float(), x[..., half:].float()
     y1 = x1 * cos - x2 * sin
     y2 = x2 * cos + x1 * sin

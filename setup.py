@@ -20,6 +20,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/cross_entropy.hip",
     "pipegoose_amd/ops/csrc/attention.hip",
     "pipegoose_amd/ops/csrc/decode_attention.hip",
+    "pipegoose_amd/ops/csrc/paged_prefill_attention.hip",
     "pipegoose_amd/ops/csrc/probes.hip",
     "pipegoose_amd/ops/csrc/rms_norm.hip",
     "pipegoose_amd/ops/csrc/rope.hip",
