@@ -7,7 +7,10 @@
 // (kv-outer dK/dV, q-outer dQ, plus a tiny delta = rowsum(dO*O) kernel),
 // recomputes P from (q, k, lse) and uses no atomics.  Tensors are [B,H,S,D]
 // logical with arbitrary strides (d contiguous); kv_off shifts the kv
-// positions (ring-attention blocks): <= -S = fully visible, 0 = causal.
+// positions (ring-attention blocks), key j is visible to row i when
+// j + kv_off <= i:  <= -S fully visible, (-S, 0) shifted causal (masked
+// elementwise, any integer), 0 causal; a positive one is rejected by the
+// host check (its first rows would see no key at all).
 //
 // Two kernel families; select_variant() in the host section at the end of
 // this file (bound as attn_variant) is the one place that picks, for the
@@ -751,8 +754,13 @@ void attn_bwd_dkdv_kernel(const bf16* __restrict__ dout,
     const float LOG2E = 1.4426950408889634f;
     const float scale2 = scale * LOG2E;
     const float slope2 = slope * LOG2E;
-    const int q_start = (kv_off <= -S) ? 0 : nb * KVROWS + kv_off;
-    for (int q0 = q_start < 0 ? 0 : q_start; q0 < S; q0 += QR) {
+    // first q row that sees this block's first kv row, rounded down to a
+    // chunk boundary: chunks stay aligned, so the last one ends at S for a
+    // kv_off that is no multiple of QR too (the rows below the diagonal that
+    // the rounding adds are masked elementwise)
+    const int q_start = (kv_off <= -S) ? 0
+        : max(0, nb * KVROWS + kv_off) & ~(QR - 1);
+    for (int q0 = q_start; q0 < S; q0 += QR) {
         __syncthreads();
         {   // stage Q and dO, row-major + transposed, plus lse/delta
             constexpr int PACKETS = (QR / 2) * (D / 8);
@@ -1678,7 +1686,13 @@ struct AttnDims {
 // attn_bwd_into, and done before anything is launched.
 AttnDims check_qkv(const char* who, const torch::Tensor& q,
                    const torch::Tensor& k, const torch::Tensor& v,
-                   const torch::Tensor& slopes) {
+                   const torch::Tensor& slopes, int64_t kv_off) {
+    // a positive offset leaves the first rows without any visible key
+    // (l = 0, o = 0 * inf) and no caller needs it; the lower bound keeps the
+    // kernels' int position arithmetic far from overflow
+    TORCH_CHECK(kv_off <= 0 && kv_off >= -(int64_t(1) << 30), who,
+                ": kv_off must be in [-2^30, 0] (0 causal, (-S, 0) shifted "
+                "causal, <= -S fully visible), got ", kv_off);
     TORCH_CHECK(q.dim() == 4 && k.dim() == 4, who,
                 ": q and k must be [B, H, S, D]");
     const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
@@ -1740,7 +1754,7 @@ std::tuple<std::string, int64_t> attn_variant(int64_t S, int64_t D) {
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor slopes,
                                     double scale, int64_t kv_off) {
-    const AttnDims d = check_qkv("attn_fwd", q, k, v, slopes);
+    const AttnDims d = check_qkv("attn_fwd", q, k, v, slopes, kv_off);
 
     // O physically [B, S, H, D]: the model reshapes attention output back to
     // [B, S, H*D] for the dense projection — this layout makes that free.
@@ -1771,7 +1785,7 @@ void attn_bwd_into(torch::Tensor dout, torch::Tensor q,
                    torch::Tensor slopes, double scale,
                    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                    int64_t kv_off) {
-    const AttnDims d = check_qkv("attn_bwd", q, k, v, slopes);
+    const AttnDims d = check_qkv("attn_bwd", q, k, v, slopes, kv_off);
     check_operand("attn_bwd", "dout", dout, q.sizes());
     check_operand("attn_bwd", "o", o, q.sizes());
     check_operand("attn_bwd", "dq", dq, q.sizes());
