@@ -186,7 +186,9 @@ class BloomAttention(nn.Module):
                 paged_prefill_attention)
             paged_prefix = S > 1 and past_kv.has_prefix(S)
             paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
-                           past_kv.block_table, past_kv.pos_t)
+                           past_kv.block_table, past_kv.pos_t,
+                           k_scale=getattr(past_kv, "k_scale", None),
+                           v_scale=getattr(past_kv, "v_scale", None))
             present = past_kv
         elif past_kv is not None:
             if hasattr(past_kv, "append"):     # StaticKVCache layer
@@ -209,13 +211,17 @@ class BloomAttention(nn.Module):
             # one query per row over its pages, per-row position
             out = paged_decode_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
-                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t,
+                k_scale=getattr(past_kv, "k_scale", None),
+                v_scale=getattr(past_kv, "v_scale", None))
         elif paged and paged_prefix:
             # S query rows at pos_t .. pos_t+S-1 over the pages, which hold
             # the prefix and (just written) the chunk itself
             out = paged_prefill_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
-                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t,
+                k_scale=getattr(past_kv, "k_scale", None),
+                v_scale=getattr(past_kv, "v_scale", None))
         elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
             # single-query decode kernel: the position is the cache's device
             # pos_t in graph mode (read in-kernel), else the last filled slot
@@ -463,15 +469,16 @@ class BloomForCausalLM(nn.Module):
                             p.dtype, p.device)
 
     def new_paged_kv_cache(self, max_seqs: int, n_pages: int, page_size: int,
-                           max_len: int):
+                           max_len: int, kv_dtype=None):
         """Paged cache bank: one page pool shared by ``max_seqs`` sequences
-        of up to ``max_len`` tokens each (models/paged_decode.py)."""
+        of up to ``max_len`` tokens each (models/paged_decode.py);
+        ``kv_dtype=torch.float8_e4m3fn`` stores it in fp8."""
         from pipegoose_amd.models.kv_cache import PagedKVCache
         attn = self.transformer.h[0].self_attention
         p = next(self.parameters())
         return PagedKVCache(len(self.transformer.h), max_seqs, n_pages,
                             page_size, max_len, attn.num_heads, attn.head_dim,
-                            p.dtype, p.device)
+                            p.dtype, p.device, kv_dtype)
 
     def gradient_checkpointing_enable(self, enabled: bool = True):
         """Recompute each block in backward instead of storing activations —

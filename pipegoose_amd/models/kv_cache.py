@@ -127,11 +127,14 @@ class PagedLayerView:
     """What ``past[i]`` is for a forward over slots ``[lo, hi)`` of a
     PagedKVCache: one layer's pools plus views (no copies) of the shared
     block table and positions.  ``paged = True`` selects the paged branch of
-    the attentions."""
+    the attentions.  ``k_scale`` / ``v_scale`` are the per-row scales of an
+    fp8 cache, ``None`` otherwise."""
     paged = True
 
-    def __init__(self, k_pool, v_pool, block_table, pos_t, rows):
+    def __init__(self, k_pool, v_pool, block_table, pos_t, rows,
+                 k_scale=None, v_scale=None):
         self.k_pool, self.v_pool = k_pool, v_pool
+        self.k_scale, self.v_scale = k_scale, v_scale
         self.block_table, self.pos_t = block_table, pos_t
         self._rows = rows
 
@@ -155,8 +158,10 @@ class PagedRows:
         self.cache, self.lo, self.hi = cache, lo, hi
         self.block_table = cache.block_table[lo:hi]
         self.pos_t = cache.pos_t[lo:hi]
-        self.layers = [PagedLayerView(k, v, self.block_table, self.pos_t, self)
-                       for k, v in zip(cache.k_pools, cache.v_pools)]
+        self.layers = [PagedLayerView(k, v, self.block_table, self.pos_t, self,
+                                      ks, vs)
+                       for k, v, ks, vs in zip(cache.k_pools, cache.v_pools,
+                                               cache.k_scales, cache.v_scales)]
 
     def __getitem__(self, i: int) -> PagedLayerView:
         return self.layers[i]
@@ -218,11 +223,17 @@ class PagedKVCache:
     held by two slots only through ``fork``, which shares WHOLE pages of a
     prefix: a shared page is full and lies below ``filled`` of every holder,
     so nobody ever writes it and no copy-on-write is needed.  Every other
-    page has exactly one holder."""
+    page has exactly one holder.
+
+    ``kv_dtype=torch.float8_e4m3fn`` stores the pools in fp8, one byte per
+    element, with per layer ``k_scales`` / ``v_scales``
+    ``[n_pages, Hkv, page_size]`` fp32 (one scale per cached row and kv head,
+    written with the row): twice the tokens per pool byte.  The scales are
+    indexed by the same page ids, so sharing a page shares its scales."""
 
     def __init__(self, n_layers: int, max_seqs: int, n_pages: int,
                  page_size: int, max_len: int, Hkv: int, D: int,
-                 dtype: torch.dtype, device):
+                 dtype: torch.dtype, device, kv_dtype=None):
         assert page_size in (16, 32, 64, 128), \
             f"page_size must be 16, 32, 64 or 128, got {page_size}"
         assert n_pages >= 2, "page 0 is reserved: n_pages must be >= 2"
@@ -231,11 +242,24 @@ class PagedKVCache:
         self.page_size = page_size
         self.max_pages = -(-max_len // page_size)
         self.max_len = self.max_pages * page_size
+        if kv_dtype is not None and kv_dtype not in (dtype,
+                                                      torch.float8_e4m3fn):
+            raise ValueError(
+                f"PagedKVCache: kv_dtype must be None, the model dtype "
+                f"{dtype} or torch.float8_e4m3fn, got {kv_dtype}")
+        self.kv_dtype = kv_dtype or dtype
+        fp8 = self.kv_dtype == torch.float8_e4m3fn
         # zeros, not empty: the reference path gathers whole pages
-        self.k_pools = [torch.zeros(n_pages, Hkv, page_size, D, dtype=dtype,
-                                    device=device) for _ in range(n_layers)]
-        self.v_pools = [torch.zeros(n_pages, Hkv, page_size, D, dtype=dtype,
-                                    device=device) for _ in range(n_layers)]
+        self.k_pools = [torch.zeros(n_pages, Hkv, page_size, D,
+                                    dtype=self.kv_dtype, device=device)
+                        for _ in range(n_layers)]
+        self.v_pools = [torch.zeros(n_pages, Hkv, page_size, D,
+                                    dtype=self.kv_dtype, device=device)
+                        for _ in range(n_layers)]
+        self.k_scales = [torch.zeros(n_pages, Hkv, page_size, device=device)
+                         if fp8 else None for _ in range(n_layers)]
+        self.v_scales = [torch.zeros(n_pages, Hkv, page_size, device=device)
+                         if fp8 else None for _ in range(n_layers)]
         self.block_table = torch.zeros(max_seqs, self.max_pages,
                                        dtype=torch.int32, device=device)
         self.table_host = torch.zeros(max_seqs, self.max_pages,

@@ -167,7 +167,9 @@ class LlamaAttention(nn.Module):
                 paged_decode_attention, paged_kv_write,
                 paged_prefill_attention)
             paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
-                           past_kv.block_table, past_kv.pos_t)
+                           past_kv.block_table, past_kv.pos_t,
+                           k_scale=getattr(past_kv, "k_scale", None),
+                           v_scale=getattr(past_kv, "v_scale", None))
             present = past_kv
         elif past_kv is not None:
             if hasattr(past_kv, "append"):     # StaticKVCache layer
@@ -200,13 +202,17 @@ class LlamaAttention(nn.Module):
             # one query per row over its pages (GQA mapped in-kernel)
             out = paged_decode_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
-                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t,
+                k_scale=getattr(past_kv, "k_scale", None),
+                v_scale=getattr(past_kv, "v_scale", None))
         elif paged_prefix:
             # S query rows at pos_t .. pos_t+S-1 over the pages, which hold
             # the prefix and (just written) the chunk itself
             out = paged_prefill_attention(
                 q, past_kv.k_pool, past_kv.v_pool, past_kv.block_table,
-                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t)
+                self._slopes_f32(q.device), self.inv_norm, past_kv.pos_t,
+                k_scale=getattr(past_kv, "k_scale", None),
+                v_scale=getattr(past_kv, "v_scale", None))
         elif (graph_mode or k.size(2) != S) and decode_kernel_supported(q, k):
             # single-query decode kernel over the un-expanded Hkv-head cache
             # (GQA mapped in-kernel); the position is the cache's device
@@ -404,15 +410,16 @@ class LlamaForCausalLM(nn.Module):
                             p.dtype, p.device)
 
     def new_paged_kv_cache(self, max_seqs: int, n_pages: int, page_size: int,
-                           max_len: int):
+                           max_len: int, kv_dtype=None):
         """Paged cache bank: one page pool shared by ``max_seqs`` sequences
-        of up to ``max_len`` tokens each (models/paged_decode.py)."""
+        of up to ``max_len`` tokens each (models/paged_decode.py);
+        ``kv_dtype=torch.float8_e4m3fn`` stores it in fp8."""
         from pipegoose_amd.models.kv_cache import PagedKVCache
         attn = self.model.layers[0].self_attn
         p = next(self.parameters())
         return PagedKVCache(len(self.model.layers), max_seqs, n_pages,
                             page_size, max_len, attn.num_kv_heads,
-                            attn.head_dim, p.dtype, p.device)
+                            attn.head_dim, p.dtype, p.device, kv_dtype)
 
     def gradient_checkpointing_enable(self, enabled: bool = True):
         """Recompute each block in backward instead of storing activations —

@@ -21,6 +21,12 @@ latency of one forward.  ``share_prefix`` lets a prompt reuse the whole pages
 of the longest token prefix it has in common with an earlier prompt of the
 same call (``PagedKVCache.fork``) and prefills only the rest.
 
+``kv_dtype=torch.float8_e4m3fn`` keeps the cache in fp8 with one fp32 scale
+per cached row and kv head (csrc/paged_fp8_attention.hip): twice the tokens
+per pool byte, about half the bytes read per decode step, at e4m3 precision
+of the cached K/V (profiles/paged_fp8_decode_attn.md).  The default is the
+model dtype.
+
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """
 from typing import List, Optional
@@ -41,12 +47,14 @@ class PagedDecoder:
     ``prompts`` is a list of up to ``max_seqs`` 1-D long tensors of any
     lengths; ``outs[i]`` holds the ``max_new_tokens`` tokens after
     ``prompts[i]``.  ``n_pages`` counts the reserved null page 0.
-    ``prefill_chunk=None`` prefills every prompt in one forward."""
+    ``prefill_chunk=None`` prefills every prompt in one forward.
+    ``kv_dtype=None`` caches in the model dtype, ``torch.float8_e4m3fn`` in
+    fp8."""
 
     def __init__(self, model, max_seqs: int, n_pages: int,
                  page_size: int = DEFAULT_PAGE_SIZE, max_len: int = 2048,
                  use_graph: Optional[bool] = None,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None, kv_dtype=None):
         assert prefill_chunk is None or prefill_chunk >= 1
         self.prefill_chunk = prefill_chunk
         ctx = getattr(model, "parallel_context", None)
@@ -58,7 +66,7 @@ class PagedDecoder:
         p = next(model.parameters())
         self.device = p.device
         self.cache = model.new_paged_kv_cache(max_seqs, n_pages, page_size,
-                                              max_len)
+                                              max_len, kv_dtype=kv_dtype)
         self.ids = torch.zeros(max_seqs, 1, dtype=torch.long,
                                device=self.device)
         self.use_graph = (p.device.type == "cuda") if use_graph is None \

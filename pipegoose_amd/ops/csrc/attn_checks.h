@@ -1,5 +1,6 @@
 // Host-side operand checks shared by the decode and paged attention ops
-// (decode_attention.hip, paged_prefill_attention.hip).
+// (decode_attention.hip, paged_prefill_attention.hip,
+// paged_fp8_attention.hip).
 #pragma once
 
 #include <torch/extension.h>
@@ -53,6 +54,80 @@ inline int check_paged(const char* op, const torch::Tensor& k_pool,
     check_operand(op, "v_pool", v_pool, {n_pages, Hkv, page, D});
     TORCH_CHECK(n_pages > 0 && n_pages < (int64_t)1 << 31 && Hkv > 0, op,
                 ": the pools must hold at least one page and one head");
+    TORCH_CHECK(block_table.is_cuda() &&
+                block_table.scalar_type() == torch::kInt, op,
+                ": block_table must be an int32 GPU tensor");
+    TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+                block_table.size(1) > 0 &&
+                (block_table.stride(1) == 1 || block_table.size(1) == 1), op,
+                ": block_table must be [", B, ", max_pages] with contiguous "
+                "rows, got sizes ", block_table.sizes());
+    TORCH_CHECK(block_table.size(1) * page < (int64_t)1 << 30, op,
+                ": max_pages * PAGE too large");
+    TORCH_CHECK(k_pool.device() == device && v_pool.device() == device &&
+                block_table.device() == device, op,
+                ": all operands must be on the same device");
+    int shift = 4;
+    while ((1 << shift) < page) ++shift;
+    return shift;
+}
+
+// an e4m3fn pool [n_pages, Hkv, PAGE, D] whose rows the kernels can read and
+// write as 8-byte packets
+inline void check_fp8_pool(const char* op, const char* name,
+                           const torch::Tensor& t, torch::IntArrayRef sizes) {
+    TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+    TORCH_CHECK(t.scalar_type() == torch::kFloat8_e4m3fn, op, ": ", name,
+                " must be float8_e4m3fn");
+    TORCH_CHECK(t.sizes() == sizes, op, ": ", name, " has sizes ",
+                t.sizes(), ", expected ", sizes);
+    TORCH_CHECK(t.stride(3) == 1, op, ": last dim of ", name,
+                " must be contiguous");
+    for (int i = 0; i < 3; ++i)
+        TORCH_CHECK(t.size(i) == 1 || t.stride(i) % 8 == 0, op, ": ",
+                    name, " stride ", i, " must be a multiple of 8 elements");
+    // the decode kernel addresses the rows of one page and head with 32 bits
+    TORCH_CHECK(t.size(2) * t.stride(2) + t.size(3) < (int64_t)1 << 31, op,
+                ": ", name, " row stride too large");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                op, ": ", name, " must be 16-byte aligned");
+}
+
+// the per-row scales [n_pages, Hkv, PAGE] of an fp8 pool
+inline void check_fp8_scale(const char* op, const char* name,
+                            const torch::Tensor& t, torch::IntArrayRef sizes,
+                            const torch::Device& device) {
+    TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+    TORCH_CHECK(t.scalar_type() == torch::kFloat, op, ": ", name,
+                " must be fp32");
+    TORCH_CHECK(t.sizes() == sizes, op, ": ", name, " has sizes ",
+                t.sizes(), ", expected ", sizes);
+    TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+    TORCH_CHECK(t.device() == device, op, ": ", name,
+                " must be on the same device as the other operands");
+}
+
+// check_paged for fp8 pools with their scales; returns log2(PAGE).
+inline int check_paged_fp8(const char* op, const torch::Tensor& k_pool,
+                           const torch::Tensor& v_pool,
+                           const torch::Tensor& k_scale,
+                           const torch::Tensor& v_scale,
+                           const torch::Tensor& block_table, int64_t B,
+                           int64_t D, const torch::Device& device) {
+    TORCH_CHECK(k_pool.dim() == 4 && v_pool.dim() == 4, op,
+                ": k_pool and v_pool must be [n_pages, Hkv, PAGE, D]");
+    const int64_t n_pages = k_pool.size(0), Hkv = k_pool.size(1);
+    const int64_t page = k_pool.size(2);
+    TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, op,
+                ": page size must be 16, 32, 64 or 128, got ", page);
+    TORCH_CHECK(D == 64 || D == 128, op,
+                ": head dim must be 64 or 128, got ", D);
+    check_fp8_pool(op, "k_pool", k_pool, {n_pages, Hkv, page, D});
+    check_fp8_pool(op, "v_pool", v_pool, {n_pages, Hkv, page, D});
+    TORCH_CHECK(n_pages > 0 && n_pages < (int64_t)1 << 31 && Hkv > 0, op,
+                ": the pools must hold at least one page and one head");
+    check_fp8_scale(op, "k_scale", k_scale, {n_pages, Hkv, page}, device);
+    check_fp8_scale(op, "v_scale", v_scale, {n_pages, Hkv, page}, device);
     TORCH_CHECK(block_table.is_cuda() &&
                 block_table.scalar_type() == torch::kInt, op,
                 ": block_table must be an int32 GPU tensor");

@@ -51,6 +51,17 @@ torch::Tensor paged_prefill_attn(torch::Tensor q, torch::Tensor k_pool,
                                  torch::Tensor block_table,
                                  torch::Tensor slopes, double scale,
                                  torch::Tensor start);
+torch::Tensor paged_decode_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
+                                    torch::Tensor v_pool,
+                                    torch::Tensor k_scale,
+                                    torch::Tensor v_scale,
+                                    torch::Tensor block_table,
+                                    torch::Tensor slopes, double scale,
+                                    torch::Tensor pos, int64_t n_splits);
+void paged_kv_write_fp8(torch::Tensor k_new, torch::Tensor v_new,
+                        torch::Tensor k_pool, torch::Tensor v_pool,
+                        torch::Tensor k_scale, torch::Tensor v_scale,
+                        torch::Tensor block_table, torch::Tensor start);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -166,6 +177,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
           py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
           py::arg("start"));
+    m.def("paged_decode_attn_fp8", &paged_decode_attn_fp8,
+          "paged_decode_attn over e4m3fn pools with fp32 scales "
+          "[n_pages, Hkv, PAGE] per cached row and kv head; same plan, "
+          "contract and bf16 output (gfx950)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+          py::arg("slopes"), py::arg("scale"), py::arg("pos"),
+          py::arg("n_splits") = 0);
+    m.def("paged_kv_write_fp8", &paged_kv_write_fp8,
+          "paged_kv_write that quantises the new bf16 rows to e4m3fn with one "
+          "fp32 scale (row amax / 448) per row and kv head (gfx950)",
+          py::arg("k_new"), py::arg("v_new"), py::arg("k_pool"),
+          py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"),
+          py::arg("block_table"), py::arg("start"));
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

@@ -86,6 +86,7 @@
 
 #include "attn_checks.h"
 #include "common.h"
+#include "decode_common.h"
 
 namespace {
 
@@ -93,73 +94,8 @@ using bf16 = __hip_bfloat16;
 using attn_checks::check_operand;
 using attn_checks::check_paged;
 using attn_checks::check_position;
-
-constexpr int TILE = 64;        // keys per workgroup iteration
-constexpr int NW = 4;           // waves per workgroup
-constexpr int MAX_SPLITS = 64;
-constexpr int TARGET_WGS = 1024;
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float bf16_lo(uint32_t w) {
-    return __uint_as_float(w << 16);
-}
-__device__ __forceinline__ float bf16_hi(uint32_t w) {
-    return __uint_as_float(w & 0xffff0000u);
-}
-__device__ __forceinline__ void unpack8(const uint4& r, float (&f)[8]) {
-    f[0] = bf16_lo(r.x); f[1] = bf16_hi(r.x);
-    f[2] = bf16_lo(r.y); f[3] = bf16_hi(r.y);
-    f[4] = bf16_lo(r.z); f[5] = bf16_hi(r.z);
-    f[6] = bf16_lo(r.w); f[7] = bf16_hi(r.w);
-}
-
-// x + (x of the lane that the DPP control selects); all lanes are active
-// wherever this is used
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(
-                   0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-
-// Sum over each aligned group of N (8 or 16) lanes, every lane of the group
-// getting the same bits: quad_perm [1,0,3,2] and [2,3,0,1] make the quads
-// uniform, row_half_mirror then pairs the two quads of an 8-lane half and
-// row_mirror the two halves of a 16-lane row.  DPP rides on the add: no LDS
-// traffic, unlike a ds_bpermute shuffle.
-template <int N>
-__device__ __forceinline__ float group_sum(float x) {
-    static_assert(N == 8 || N == 16, "one row is 8 or 16 lanes");
-    x = dpp_add<0xB1>(x);
-    x = dpp_add<0x4E>(x);
-    x = dpp_add<0x141>(x);
-    if constexpr (N == 16) x = dpp_add<0x140>(x);
-    return x;
-}
-
-// the query position of batch row b, clamped into the cache
-__device__ __forceinline__ int load_pos(const int64_t* __restrict__ pos,
-                                        int pos_n, int pos_scalar, int b,
-                                        int Skv) {
-    int64_t p = pos ? pos[pos_n == 1 ? 0 : b] : (int64_t)pos_scalar;
-    p = p < 0 ? 0 : p;
-    return (int)(p > Skv - 1 ? Skv - 1 : p);
-}
-
-// Merges online-softmax state (m2, l2, a2) into (m, l, a).  Both maxima are
-// finite (-FLT_MAX when a state saw no key): the exponents are <= 0 and an
-// empty state has l = 0, a = 0, so it contributes nothing.
-template <int N>
-__device__ __forceinline__ void merge_state(float& m, float& l, float (&a)[N],
-                                            float m2, float l2,
-                                            const float (&a2)[N]) {
-    const float mn = fmaxf(m, m2);
-    const float w1 = __builtin_amdgcn_exp2f(m - mn);
-    const float w2 = __builtin_amdgcn_exp2f(m2 - mn);
-    m = mn;
-    l = l * w1 + l2 * w2;
-#pragma unroll
-    for (int e = 0; e < N; ++e) a[e] = a[e] * w1 + a2[e] * w2;
-}
+// TILE, NW, the plan, group_sum, load_pos and merge_state
+using namespace decode_common;
 
 // GT q heads of the group are processed per pass over the split's keys
 // (GT = 4, 2 or 1, the largest that divides G); G > 4 takes G/GT passes, the
@@ -372,33 +308,6 @@ void decode_attn_combine_kernel(const float* __restrict__ part_acc,
     o[((int64_t)b * H + h) * D + d] = __float2bfloat16(num / den);
 }
 
-struct DecodePlan {
-    int n_splits, chunk;
-};
-
-int round_up(int64_t x, int64_t to) { return (int)((x + to - 1) / to * to); }
-
-// The plan of the file header: shapes only, never the position.
-DecodePlan make_plan(int64_t B, int64_t Hkv, int64_t Skv, int64_t D,
-                     int64_t forced) {
-    TORCH_CHECK(B > 0 && Hkv > 0 && Skv > 0,
-                "decode_attn: B, Hkv and Skv must be positive");
-    TORCH_CHECK(D == 64 || D == 128,
-                "decode_attn: head dim must be 64 or 128, got ", D);
-    TORCH_CHECK(forced >= 0 && forced <= MAX_SPLITS,
-                "decode_attn: n_splits must be 0 (auto) or 1..", MAX_SPLITS,
-                ", got ", forced);
-    TORCH_CHECK(Skv < (int64_t)1 << 30, "decode_attn: Skv too large");
-    if (forced > 0)
-        return {(int)forced, round_up((Skv + forced - 1) / forced, TILE)};
-    int64_t n = (TARGET_WGS + B * Hkv - 1) / (B * Hkv);
-    n = std::min<int64_t>(n, std::min<int64_t>(MAX_SPLITS,
-                                               (Skv + TILE - 1) / TILE));
-    n = std::max<int64_t>(n, 1);
-    const int chunk = round_up((Skv + n - 1) / n, TILE);
-    return {(int)((Skv + chunk - 1) / chunk), chunk};
-}
-
 // One thread per 16-byte packet of a new row; K and V in the same launch.
 // Rows whose logical position falls outside [0, capacity) are dropped.
 template <int D>
@@ -487,22 +396,32 @@ torch::Tensor launch_decode(const torch::Tensor& q, const torch::Tensor& k,
     else with_gt(std::integral_constant<int, 128>{});
     HIP_CHECK_LAUNCH();
 
-    auto launch_combine = [&](auto dv_) {
-        constexpr int DV = decltype(dv_)::value;
-        hipLaunchKernelGGL((decode_attn_combine_kernel<DV>), dim3(H, B),
-                           dim3(DV), 0, stream, part_acc.data_ptr<float>(),
-                           part_ml.data_ptr<float>(), pos_ptr, pos_n,
-                           (int)(Skv - 1),
-                           reinterpret_cast<bf16*>(o_phys.data_ptr()), (int)H,
-                           (int)Skv, plan.chunk, plan.n_splits);
-    };
-    if (D == 64) launch_combine(std::integral_constant<int, 64>{});
-    else launch_combine(std::integral_constant<int, 128>{});
-    HIP_CHECK_LAUNCH();
+    launch_combine(part_acc.data_ptr<float>(), part_ml.data_ptr<float>(),
+                   pos_ptr, pos_n, (int)(Skv - 1),
+                   reinterpret_cast<bf16*>(o_phys.data_ptr()), B, H, D, Skv,
+                   plan);
     return o_phys.permute({0, 2, 1, 3});
 }
 
 }  // namespace
+
+void decode_common::launch_combine(const float* part_acc,
+                                   const float* part_ml, const int64_t* pos,
+                                   int pos_n, int pos_scalar, bf16* o,
+                                   int64_t B, int64_t H, int64_t D,
+                                   int64_t Skv, const DecodePlan& plan) {
+    auto stream = at::cuda::getCurrentCUDAStream();
+    auto launch = [&](auto dv_) {
+        constexpr int DV = decltype(dv_)::value;
+        hipLaunchKernelGGL((decode_attn_combine_kernel<DV>), dim3(H, B),
+                           dim3(DV), 0, stream, part_acc, part_ml, pos, pos_n,
+                           pos_scalar, o, (int)H, (int)Skv, plan.chunk,
+                           plan.n_splits);
+    };
+    if (D == 64) launch(std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 128>{});
+    HIP_CHECK_LAUNCH();
+}
 
 std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t Hkv,
                                               int64_t Skv, int64_t D) {

@@ -17,6 +17,15 @@ csrc/paged_prefill_attention.hip for ``Sq > 1`` query rows at positions
 outside ``[0, max_pages * PAGE)`` giving zeros.  Everything else (CPU, fp32,
 other head dims, ``PG_DECODE_ATTN=0``) runs the pure-torch references.
 Inference only — there is no backward.
+
+fp8 cache (``k_scale`` / ``v_scale`` given): the pools are
+``torch.float8_e4m3fn`` and every cached row of every kv head has an fp32
+scale in ``[n_pages, Hkv, PAGE]`` tensors indexed by the same page ids; a row
+is quantised when it is written (``scale = amax / 448``, no calibration) and
+reads back as ``float(byte) * scale``.  GPU path: ``paged_kv_write_fp8`` and
+``paged_decode_attn_fp8`` of csrc/paged_fp8_attention.hip under the same
+conditions and rules as the bf16 kernels; prefill over an fp8 cache runs the
+reference on the dequantised gather.
 """
 import torch
 
@@ -37,31 +46,53 @@ def paged_gather(pool: torch.Tensor, block_table: torch.Tensor,
     return rows[:, :, :n_rows]
 
 
+def paged_gather_dequant(pool: torch.Tensor, scale: torch.Tensor,
+                         block_table: torch.Tensor, n_rows: int,
+                         dtype: torch.dtype) -> torch.Tensor:
+    """``paged_gather`` of an fp8 pool with its scales [n_pages, Hkv, PAGE],
+    dequantised: ``float(byte) * scale`` in ``dtype`` or wider (the product
+    with the fp32 scale is not rounded down to a narrower ``dtype``)."""
+    # gathered as bytes: indexing lacks fp8 on some devices
+    rows = paged_gather(pool.view(torch.uint8), block_table, n_rows)
+    return rows.view(pool.dtype).to(dtype) \
+        * paged_gather(scale[..., None], block_table, n_rows)
+
+
+def _gathered(pool, scale, block_table, n_rows, dtype):
+    if scale is None:
+        return paged_gather(pool, block_table, n_rows)
+    return paged_gather_dequant(pool, scale, block_table, n_rows, dtype)
+
+
 def paged_decode_attention_reference(q, k_pool, v_pool, block_table, slopes,
-                                     scale, pos):
-    """``decode_attention_reference`` on the gathered cache, in the dtype of
-    ``q`` (fp64 in, fp64 oracle out)."""
+                                     scale, pos, k_scale=None, v_scale=None):
+    """``decode_attention_reference`` on the gathered cache (dequantised when
+    the scales of an fp8 cache are given), in the dtype of ``q`` (fp64 in,
+    fp64 oracle out)."""
     n_rows = block_table.size(1) * k_pool.size(2)
     return decode_attention_reference(
-        q, paged_gather(k_pool, block_table, n_rows),
-        paged_gather(v_pool, block_table, n_rows), slopes, scale, pos)
+        q, _gathered(k_pool, k_scale, block_table, n_rows, q.dtype),
+        _gathered(v_pool, v_scale, block_table, n_rows, q.dtype), slopes,
+        scale, pos)
 
 
 def paged_prefill_attention_reference(q, k_pool, v_pool, block_table, slopes,
-                                      scale, start):
+                                      scale, start, k_scale=None,
+                                      v_scale=None):
     """Pure-torch definition of prefill attention over the paged cache, in the
     dtype of ``q`` (fp64 in, fp64 oracle out).
 
     q [B,H,Sq,D]; row ``i`` of batch row ``b`` sits at ``p = start[b] + i``
     and sees keys ``0..p`` of the gathered cache with bias
     ``slopes[h] * (j - p)``.  Rows with ``p`` outside
-    ``[0, max_pages * PAGE)`` give zeros.  Returns [B,H,Sq,D]."""
+    ``[0, max_pages * PAGE)`` give zeros.  With the scales of an fp8 cache
+    the gather is dequantised.  Returns [B,H,Sq,D]."""
     B, H, Sq, D = q.shape
     Hkv = k_pool.size(1)
     G = H // Hkv
     cap = block_table.size(1) * k_pool.size(2)
-    k = paged_gather(k_pool, block_table, cap).to(q.dtype)
-    v = paged_gather(v_pool, block_table, cap).to(q.dtype)
+    k = _gathered(k_pool, k_scale, block_table, cap, q.dtype).to(q.dtype)
+    v = _gathered(v_pool, v_scale, block_table, cap, q.dtype).to(q.dtype)
     st = start.to(device=q.device, dtype=torch.long).reshape(-1).expand(B)
     p = st[:, None] + torch.arange(Sq, device=q.device)            # [B, Sq]
     in_range = (p >= 0) & (p < cap)
@@ -101,6 +132,40 @@ def paged_kv_write_reference(k_new, v_new, k_pool, v_pool, block_table, start):
     v_pool[ids, :, slot] = v_new.transpose(1, 2)[keep].to(v_pool.dtype)
 
 
+def quantize_rows_fp8(x: torch.Tensor):
+    """The cache format's quantiser on the rows ``x[..., :]``: e4m3fn bytes
+    of ``clamp(x * (448 / amax), -448, 448)`` and the fp32 scales
+    ``amax / 448`` (shape of ``x`` without its last dim); an all-zero row
+    gives scale 0 and zero bytes."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1, keepdim=True)
+    inv = torch.where(amax > 0, 448.0 / amax, torch.zeros_like(amax))
+    q = (xf * inv).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q, (amax / 448.0).squeeze(-1)
+
+
+def paged_kv_write_fp8_reference(k_new, v_new, k_pool, v_pool, k_scale,
+                                 v_scale, block_table, start):
+    """``paged_kv_write_reference`` into an fp8 cache: every kept row of
+    every kv head is quantised on its own (``quantize_rows_fp8``) and its
+    bytes and scale are written in place."""
+    B, _, S_new, _ = k_new.shape
+    page = k_pool.size(2)
+    capacity = block_table.size(1) * page
+    st = start.to(device=k_new.device, dtype=torch.long).reshape(-1).expand(B)
+    row = st[:, None] + torch.arange(S_new, device=k_new.device)   # [B, S]
+    keep = (row >= 0) & (row < capacity)
+    safe = row.clamp(0, capacity - 1)
+    ids = block_table.long().gather(1, safe // page)[keep]         # [n]
+    slot = (safe % page)[keep]
+    for new, pool, scales in ((k_new, k_pool, k_scale),
+                              (v_new, v_pool, v_scale)):
+        q, sc = quantize_rows_fp8(new.transpose(1, 2)[keep])  # [n, Hkv, D]
+        # assigned as bytes: indexed assignment lacks fp8 on some devices
+        pool.view(torch.uint8)[ids, :, slot] = q.view(torch.uint8)
+        scales[ids, :, slot] = sc
+
+
 def paged_kernel_supported(q: torch.Tensor, k_pool: torch.Tensor) -> bool:
     """Whether the HIP paged kernels take these operands: the conditions of
     ``decode_kernel_supported`` (GPU, bf16, extension present, D in
@@ -117,6 +182,28 @@ def paged_kernel_supported(q: torch.Tensor, k_pool: torch.Tensor) -> bool:
         and k_pool.size(2) in (16, 32, 64, 128)
 
 
+def paged_fp8_kernel_supported(q: torch.Tensor, k_pool: torch.Tensor) -> bool:
+    """``paged_kernel_supported`` for an fp8 cache: the same conditions on
+    ``q`` (GPU, bf16, extension present, D in {64, 128},
+    ``PG_DECODE_ATTN != "0"``) and on the page size, with e4m3fn pools on the
+    GPU.  Not gated on speed: fp8 is opt-in and its capacity gain holds
+    whatever the kernel times (profiles/paged_fp8_decode_attn.md)."""
+    q1 = q[:, :, :1]
+    # q1 also stands in for the bf16 cache operand of the decode condition
+    return k_pool.dtype == torch.float8_e4m3fn and k_pool.is_cuda \
+        and decode_kernel_supported(q1, q1) \
+        and k_pool.size(2) in (16, 32, 64, 128)
+
+
+def _check_scales(name, k_pool, k_scale, v_scale):
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError(f"{name}: k_scale and v_scale go together")
+    if k_scale is not None and k_pool.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{name}: scales are for float8_e4m3fn pools, got "
+                         f"{k_pool.dtype}")
+    return k_scale is not None
+
+
 def _inference_only(name, tensors):
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in tensors):
@@ -125,10 +212,22 @@ def _inference_only(name, tensors):
             "torch.no_grad() or with tensors that do not require grad")
 
 
-def paged_decode_attention(q, k_pool, v_pool, block_table, slopes, scale, pos):
+def paged_decode_attention(q, k_pool, v_pool, block_table, slopes, scale, pos,
+                           k_scale=None, v_scale=None):
     """The kernel when ``paged_kernel_supported``, else the reference.
-    Logical [B,H,1,D]; the kernel's result is physically [B,1,H,D]."""
+    Logical [B,H,1,D]; the kernel's result is physically [B,1,H,D].  With
+    ``k_scale`` / ``v_scale`` the pools are an fp8 cache: the fp8 kernel when
+    ``paged_fp8_kernel_supported``, else the reference on the dequantised
+    gather."""
     _inference_only("paged_decode_attention", (q, k_pool, v_pool, slopes))
+    if _check_scales("paged_decode_attention", k_pool, k_scale, v_scale):
+        if not (q.size(-2) == 1 and paged_fp8_kernel_supported(q, k_pool)):
+            return paged_decode_attention_reference(
+                q, k_pool, v_pool, block_table, slopes, scale, pos,
+                k_scale, v_scale)
+        return get_extension(required=True).paged_decode_attn_fp8(
+            q, k_pool, v_pool, k_scale, v_scale, block_table,
+            slopes.to(device=q.device, dtype=torch.float32), scale, pos, 0)
     if not (q.size(-2) == 1 and paged_kernel_supported(q, k_pool)):
         return paged_decode_attention_reference(
             q, k_pool, v_pool, block_table, slopes, scale, pos)
@@ -139,12 +238,21 @@ def paged_decode_attention(q, k_pool, v_pool, block_table, slopes, scale, pos):
 
 
 def paged_prefill_attention(q, k_pool, v_pool, block_table, slopes, scale,
-                            start):
+                            start, k_scale=None, v_scale=None):
     """Attention of the ``Sq >= 1`` rows of ``q`` [B,H,Sq,D] at positions
     ``start[b] + i`` over the pools, which already hold the rows' own K/V:
     the kernel when ``paged_kernel_supported``, else the reference.  The
-    kernel's result is physically [B,Sq,H,D]."""
+    kernel's result is physically [B,Sq,H,D].
+
+    With ``k_scale`` / ``v_scale`` (fp8 cache) this ALWAYS runs the reference
+    on the dequantised gather, in the dtype of ``q``: an fp8 prefill kernel
+    is the follow-up, and chunked prefill and prefix sharing work on an fp8
+    cache meanwhile."""
     _inference_only("paged_prefill_attention", (q, k_pool, v_pool, slopes))
+    if _check_scales("paged_prefill_attention", k_pool, k_scale, v_scale):
+        return paged_prefill_attention_reference(
+            q, k_pool, v_pool, block_table, slopes, scale, start,
+            k_scale, v_scale)
     if not paged_kernel_supported(q, k_pool):
         return paged_prefill_attention_reference(
             q, k_pool, v_pool, block_table, slopes, scale, start)
@@ -154,10 +262,22 @@ def paged_prefill_attention(q, k_pool, v_pool, block_table, slopes, scale,
         slopes.to(device=q.device, dtype=torch.float32), scale, start)
 
 
-def paged_kv_write(k_new, v_new, k_pool, v_pool, block_table, start):
+def paged_kv_write(k_new, v_new, k_pool, v_pool, block_table, start,
+                   k_scale=None, v_scale=None):
     """Write the new rows into the pools (in place): the kernel when
-    ``paged_kernel_supported``, else the reference."""
+    ``paged_kernel_supported``, else the reference.  With ``k_scale`` /
+    ``v_scale`` (fp8 cache) the rows are quantised and their scales written
+    too: the fp8 kernel when ``paged_fp8_kernel_supported``, else
+    ``paged_kv_write_fp8_reference``."""
     _inference_only("paged_kv_write", (k_new, v_new, k_pool, v_pool))
+    if _check_scales("paged_kv_write", k_pool, k_scale, v_scale):
+        if not paged_fp8_kernel_supported(k_new, k_pool):
+            return paged_kv_write_fp8_reference(
+                k_new, v_new, k_pool, v_pool, k_scale, v_scale, block_table,
+                start)
+        return get_extension(required=True).paged_kv_write_fp8(
+            k_new, v_new, k_pool, v_pool, k_scale, v_scale, block_table,
+            start)
     if not paged_kernel_supported(k_new, k_pool):
         return paged_kv_write_reference(k_new, v_new, k_pool, v_pool,
                                         block_table, start)
