@@ -24,8 +24,10 @@ same call (``PagedKVCache.fork``) and prefills only the rest.
 ``kv_dtype=torch.float8_e4m3fn`` keeps the cache in fp8 with one fp32 scale
 per cached row and kv head (csrc/paged_fp8_attention.hip): twice the tokens
 per pool byte, about half the bytes read per decode step, at e4m3 precision
-of the cached K/V (profiles/paged_fp8_decode_attn.md).  The default is the
-model dtype.
+of the cached K/V (profiles/paged_fp8_decode_attn.md).  Chunked prefill and
+shared prefixes attend over the fp8 pages in a kernel as well
+(csrc/paged_fp8_prefill_attention.hip, profiles/paged_fp8_prefill_attn.md).
+The default is the model dtype.
 
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """

@@ -62,6 +62,13 @@ void paged_kv_write_fp8(torch::Tensor k_new, torch::Tensor v_new,
                         torch::Tensor k_pool, torch::Tensor v_pool,
                         torch::Tensor k_scale, torch::Tensor v_scale,
                         torch::Tensor block_table, torch::Tensor start);
+torch::Tensor paged_prefill_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
+                                     torch::Tensor v_pool,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_scale,
+                                     torch::Tensor block_table,
+                                     torch::Tensor slopes, double scale,
+                                     torch::Tensor start);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -191,6 +198,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_new"), py::arg("v_new"), py::arg("k_pool"),
           py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"),
           py::arg("block_table"), py::arg("start"));
+    m.def("paged_prefill_attn_fp8", &paged_prefill_attn_fp8,
+          "paged_prefill_attn over e4m3fn pools with fp32 scales "
+          "[n_pages, Hkv, PAGE] per cached row and kv head; same contract "
+          "and bf16 output, no scale beyond the last visible row read "
+          "(gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+          py::arg("slopes"), py::arg("scale"), py::arg("start"));
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

@@ -1,6 +1,7 @@
 // Device helpers and the split-KV plan shared by the decode attention kernels
 // (decode_attention.hip: bf16, contiguous and paged; paged_fp8_attention.hip:
-// fp8 pools), and the launcher of the combine kernel, which lives in
+// fp8 pools) and by the fp8 prefill kernel (paged_fp8_prefill_attention.hip),
+// and the launcher of the combine kernel, which lives in
 // decode_attention.hip.  The design is described in that file's header.
 //
 // The device helpers use compiler builtins only (no functions of the HIP
@@ -57,6 +58,37 @@ __device__ __forceinline__ float group_sum(float x) {
     x = dpp_add<0x141>(x);
     if constexpr (N == 16) x = dpp_add<0x140>(x);
     return x;
+}
+
+// max(x, x of the lane that the DPP control selects); whole groups active
+template <int CTRL>
+__device__ __forceinline__ float dpp_max(float x) {
+    return __builtin_fmaxf(
+        x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+               0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true)));
+}
+
+// group_sum's butterfly with max: every lane of an aligned group of N lanes
+// gets the group's maximum
+template <int N>
+__device__ __forceinline__ float group_max(float x) {
+    static_assert(N == 8 || N == 16, "one row is 8 or 16 lanes");
+    x = dpp_max<0xB1>(x);
+    x = dpp_max<0x4E>(x);
+    x = dpp_max<0x141>(x);
+    if constexpr (N == 16) x = dpp_max<0x140>(x);
+    return x;
+}
+
+__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+
+// what __syncthreads() is: a workgroup barrier between a release and an
+// acquire fence of workgroup scope
+__device__ __forceinline__ void block_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // the query position of batch row b, clamped into the cache

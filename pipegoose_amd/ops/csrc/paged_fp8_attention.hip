@@ -69,17 +69,6 @@ using namespace decode_common;
 
 constexpr float E4M3_MAX = 448.0f;
 
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-// what __syncthreads() is: a workgroup barrier between a release and an
-// acquire fence of workgroup scope
-__device__ __forceinline__ void block_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
 // the 8 e4m3fn of an 8-byte packet; fp8 -> fp32 is exact
@@ -97,26 +86,6 @@ __device__ __forceinline__ void unpack8_fp8(const uint2& r, float (&f)[8]) {
 __device__ __forceinline__ float lane_xor(float x, int lane, int off) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(
         (lane ^ off) << 2, __builtin_bit_cast(int, x)));
-}
-
-// max(x, x of the lane that the DPP control selects); whole groups active
-template <int CTRL>
-__device__ __forceinline__ float dpp_max(float x) {
-    return __builtin_fmaxf(
-        x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-               0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true)));
-}
-
-// group_sum's butterfly with max: every lane of an aligned group of N lanes
-// gets the group's maximum
-template <int N>
-__device__ __forceinline__ float group_max(float x) {
-    static_assert(N == 8 || N == 16, "one row is 8 or 16 lanes");
-    x = dpp_max<0xB1>(x);
-    x = dpp_max<0x4E>(x);
-    x = dpp_max<0x141>(x);
-    if constexpr (N == 16) x = dpp_max<0x140>(x);
-    return x;
 }
 
 // Quantises this lane's 8 values of a row whose other values sit in the

@@ -23,9 +23,10 @@ fp8 cache (``k_scale`` / ``v_scale`` given): the pools are
 scale in ``[n_pages, Hkv, PAGE]`` tensors indexed by the same page ids; a row
 is quantised when it is written (``scale = amax / 448``, no calibration) and
 reads back as ``float(byte) * scale``.  GPU path: ``paged_kv_write_fp8`` and
-``paged_decode_attn_fp8`` of csrc/paged_fp8_attention.hip under the same
-conditions and rules as the bf16 kernels; prefill over an fp8 cache runs the
-reference on the dequantised gather.
+``paged_decode_attn_fp8`` of csrc/paged_fp8_attention.hip and
+``paged_prefill_attn_fp8`` of csrc/paged_fp8_prefill_attention.hip, under
+the same conditions and rules as the bf16 kernels; no scale beyond the last
+visible row is read either.
 """
 import torch
 
@@ -186,8 +187,13 @@ def paged_fp8_kernel_supported(q: torch.Tensor, k_pool: torch.Tensor) -> bool:
     """``paged_kernel_supported`` for an fp8 cache: the same conditions on
     ``q`` (GPU, bf16, extension present, D in {64, 128},
     ``PG_DECODE_ATTN != "0"``) and on the page size, with e4m3fn pools on the
-    GPU.  Not gated on speed: fp8 is opt-in and its capacity gain holds
-    whatever the kernel times (profiles/paged_fp8_decode_attn.md)."""
+    GPU.  ``q`` may hold any number of rows: the write and the prefill
+    kernel use the same condition.  Not gated on speed: fp8 is opt-in, and
+    what it buys is capacity (twice the tokens per pool byte) and, for
+    prefill, activation memory bounded by the chunk — the reference
+    materialises the dequantised cache at full capacity and a score tensor
+    over it — and both hold whatever the kernels time
+    (profiles/paged_fp8_decode_attn.md, profiles/paged_fp8_prefill_attn.md)."""
     q1 = q[:, :, :1]
     # q1 also stands in for the bf16 cache operand of the decode condition
     return k_pool.dtype == torch.float8_e4m3fn and k_pool.is_cuda \
@@ -244,15 +250,18 @@ def paged_prefill_attention(q, k_pool, v_pool, block_table, slopes, scale,
     the kernel when ``paged_kernel_supported``, else the reference.  The
     kernel's result is physically [B,Sq,H,D].
 
-    With ``k_scale`` / ``v_scale`` (fp8 cache) this ALWAYS runs the reference
-    on the dequantised gather, in the dtype of ``q``: an fp8 prefill kernel
-    is the follow-up, and chunked prefill and prefix sharing work on an fp8
-    cache meanwhile."""
+    With ``k_scale`` / ``v_scale`` the pools are an fp8 cache: the fp8
+    kernel when ``paged_fp8_kernel_supported``, else the reference on the
+    dequantised gather, in the dtype of ``q``."""
     _inference_only("paged_prefill_attention", (q, k_pool, v_pool, slopes))
     if _check_scales("paged_prefill_attention", k_pool, k_scale, v_scale):
-        return paged_prefill_attention_reference(
-            q, k_pool, v_pool, block_table, slopes, scale, start,
-            k_scale, v_scale)
+        if not paged_fp8_kernel_supported(q, k_pool):
+            return paged_prefill_attention_reference(
+                q, k_pool, v_pool, block_table, slopes, scale, start,
+                k_scale, v_scale)
+        return get_extension(required=True).paged_prefill_attn_fp8(
+            q, k_pool, v_pool, k_scale, v_scale, block_table,
+            slopes.to(device=q.device, dtype=torch.float32), scale, start)
     if not paged_kernel_supported(q, k_pool):
         return paged_prefill_attention_reference(
             q, k_pool, v_pool, block_table, slopes, scale, start)

@@ -24,6 +24,21 @@ K/V rotate over several pools (>= 1 GB in total) so that no call finds its
 operands in the 256 MiB L3.  Before timing, the kernel's result must agree
 with gather+sdpa to bf16 accuracy.
 
+``--kv fp8``: the same rows over an fp8 cache
+(ops/csrc/paged_fp8_prefill_attention.hip), every page size a row of its own.
+Timed, alternating as above:
+
+  fp8           ``paged_prefill_attn_fp8`` on e4m3fn pools with their scales
+  reference     what the dispatch ran before that kernel existed and still
+                runs without it: ``paged_prefill_attention_reference`` on the
+                dequantised gather, in bf16
+  bf16          ``paged_prefill_attn`` on the bf16 pools the fp8 ones were
+                quantised from
+
+Before timing, fp8 must agree with reference to bf16 accuracy.  The first row
+of every shape also records ``torch.cuda.max_memory_allocated`` above the
+resident operands for one call of fp8 and of reference.
+
 End to end (``--e2e``): bloom-560m, a 2048-token prompt through PagedDecoder —
 time to first token whole against ``prefill_chunk=512``, and two prompts that
 share 1536 tokens with and without ``share_prefix``.
@@ -165,6 +180,118 @@ def run_shape(name, sqs, contexts, pages, iters, repeats, warmup):
             }), flush=True)
 
 
+def run_shape_fp8(name, sqs, contexts, pages, iters, repeats, warmup):
+    import torch
+    from pipegoose_amd.models.bloom import alibi_slopes
+    from pipegoose_amd.ops import get_extension
+    from pipegoose_amd.ops.paged_attention import (
+        paged_prefill_attention_reference, quantize_rows_fp8)
+
+    assert torch.cuda.is_available(), "paged_prefill_attn_bench needs a GPU"
+    ext = get_extension(required=True)
+    B, H, Hkv, D, alibi = SHAPES[name]
+    dev = "cuda"
+    torch.manual_seed(0)
+    scale = D ** -0.5
+    slopes = (alibi_slopes(H) if alibi else torch.zeros(H)).to(dev).float()
+    max_len = max(contexts) + max(sqs)
+    max_len = -(-max_len // max(pages)) * max(pages)
+    kv_bytes = 2 * B * Hkv * max_len * D * 2
+    n_buf = max(2, min(8, -(-(1 << 30) // kv_bytes)))
+    start_t = torch.zeros(1, dtype=torch.long, device=dev)
+
+    def timed(fn):
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        for i in range(iters):
+            fn(i)
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) * 1e3 / iters      # us per call
+
+    def peak_mb(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fn(0)
+        torch.cuda.synchronize()
+        return round((torch.cuda.max_memory_allocated() - base) / 1e6, 1)
+
+    first = True
+    for page in pages:
+        max_pages = max_len // page
+        n_pages = B * max_pages + 1                     # + the null page
+        table = (torch.randperm(n_pages - 1, device=dev) + 1).view(
+            B, max_pages).to(torch.int32)
+        bufs = []
+        for _ in range(n_buf):
+            row = []
+            for _kv in range(2):
+                pool = torch.randn(n_pages, Hkv, page, D, device=dev).bfloat16()
+                row += [pool, *quantize_rows_fp8(pool)]
+            bufs.append(row)        # k bf16, k fp8, k scale, v bf16, v fp8, ..
+        for Sq in sqs:
+            q = torch.randn(B, Sq, H, D, device=dev).bfloat16().transpose(1, 2)
+            for context in contexts:
+                start_t.fill_(context)
+
+                def fp8(i):
+                    kb, k8, ks, vb, v8, vs = bufs[i % n_buf]
+                    return ext.paged_prefill_attn_fp8(
+                        q, k8, v8, ks, vs, table, slopes, scale, start_t)
+
+                def reference(i):
+                    kb, k8, ks, vb, v8, vs = bufs[i % n_buf]
+                    return paged_prefill_attention_reference(
+                        q, k8, v8, table, slopes, scale, start_t, ks, vs)
+
+                def bf16(i):
+                    kb, k8, ks, vb, v8, vs = bufs[i % n_buf]
+                    return ext.paged_prefill_attn(
+                        q, kb, vb, table, slopes, scale, start_t)
+                paths = {"fp8": fp8, "reference": reference, "bf16": bf16}
+
+                # results must agree before a time means anything
+                want = reference(0).float()
+                err = (fp8(0).float() - want).abs().max().item()
+                assert err <= 2.0 ** -5 * max(1.0, want.abs().max().item()), \
+                    f"kernel differs from reference by {err} at {Sq}/{context}"
+                del want
+                for i in range(warmup):
+                    for fn in paths.values():
+                        fn(i)
+                torch.cuda.synchronize()
+                times = {label: [] for label in paths}
+                for _ in range(repeats):               # alternate the paths
+                    for label, fn in paths.items():
+                        times[label].append(timed(fn))
+                med = {label: statistics.median(t)
+                       for label, t in times.items()}
+                flops = attn_flops(B, H, D, Sq, context)
+                line = {
+                    "shape": name, "kv": "fp8", "B": B, "H": H, "Hkv": Hkv,
+                    "D": D, "page": page, "Sq": Sq, "context": context,
+                    "kv_buffers": n_buf, "GFLOP": round(flops / 1e9, 2),
+                    "us": {label: round(t, 1) for label, t in med.items()},
+                    "us_all": {label: [round(x, 1) for x in t]
+                               for label, t in times.items()},
+                    "spread_pct": {
+                        label: round(100 * (max(t) - min(t)) / med[label], 1)
+                        for label, t in times.items()},
+                    "fp8_TFLOPs": round(flops / med["fp8"] / 1e6, 1),
+                    "fp8_over_reference": round(med["fp8"] / med["reference"],
+                                                4),
+                    "fp8_over_bf16": round(med["fp8"] / med["bf16"], 3),
+                    "max_abs_diff_to_reference": round(err, 5)}
+                if first:
+                    line["peak_MB"] = {"fp8": peak_mb(fp8),
+                                       "reference": peak_mb(reference)}
+                    first = False
+                print(json.dumps(line), flush=True)
+        del bufs
+
+
 def run_e2e(prompt_len, chunk, shared, repeats):
     """bloom-560m through PagedDecoder: time to first token (one new token,
     so no decode step runs), host clock around a device synchronise."""
@@ -231,6 +358,9 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the fp8 kernel against the reference on the "
+                         "dequantised gather and against the bf16 kernel")
     ap.add_argument("--e2e", action="store_true",
                     help="the end-to-end PagedDecoder timings instead")
     ap.add_argument("--prompt", type=int, default=2048)
@@ -245,11 +375,12 @@ def main():
         run_e2e(args.prompt, args.chunk, args.shared, args.repeats)
         return
     if args.child:
-        run_shape(args.child, args.sq, args.context, args.pages, args.iters,
-                  args.repeats, args.warmup)
+        run = run_shape_fp8 if args.kv == "fp8" else run_shape
+        run(args.child, args.sq, args.context, args.pages, args.iters,
+            args.repeats, args.warmup)
         return
     common = ["--iters", str(args.iters), "--repeats", str(args.repeats),
-              "--warmup", str(args.warmup)]
+              "--warmup", str(args.warmup), "--kv", args.kv]
     if args.e2e:
         jobs = {"e2e": ["--prompt", str(args.prompt), "--chunk",
                         str(args.chunk), "--shared", str(args.shared)]}
