@@ -128,12 +128,19 @@ class LlamaAttention(nn.Module):
                                                      False)
         paged = getattr(past_kv, "paged", False)
         paged_prefix = paged and S > 1 and past_kv.has_prefix(S)
-        if paged and (S == 1 or paged_prefix):
+        paged_fused = paged and (S == 1 or paged_prefix)
+        if paged_fused:
             # paged decode, or a prefill chunk behind a cached prefix: row i
-            # sits at its sequence's own device position + i
-            from pipegoose_amd.ops.rope import rope_at_position
-            q = rope_at_position(q, self.rope_theta, past_kv.pos_t)
-            k = rope_at_position(k, self.rope_theta, past_kv.pos_t)
+            # sits at its sequence's own device position + i.  One launch
+            # rotates q and k there and writes the rotated k and v through
+            # the block table (csrc/paged_rope_write.hip); attention then
+            # reads everything from the pools.
+            from pipegoose_amd.ops.paged_attention import paged_rope_write
+            q = paged_rope_write(q, k, v, past_kv.k_pool, past_kv.v_pool,
+                                 past_kv.block_table, past_kv.pos_t,
+                                 self.rope_theta,
+                                 k_scale=getattr(past_kv, "k_scale", None),
+                                 v_scale=getattr(past_kv, "v_scale", None))
         elif paged:
             # a multi-token forward into empty slots starts at position 0
             q = apply_rope(q, self.rope_theta, pos_offset=0)
@@ -160,16 +167,17 @@ class LlamaAttention(nn.Module):
         present = None
         if paged:
             # paged cache (models/kv_cache.py PagedKVCache): the new rows go
-            # through the block table at each row's own device position;
-            # k, v stay the fresh rows, which a prefill into empty slots
-            # attends over
+            # through the block table at each row's own device position
+            # (already there after paged_rope_write); k, v stay the fresh
+            # rows, which a prefill into empty slots attends over
             from pipegoose_amd.ops.paged_attention import (
                 paged_decode_attention, paged_kv_write,
                 paged_prefill_attention)
-            paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
-                           past_kv.block_table, past_kv.pos_t,
-                           k_scale=getattr(past_kv, "k_scale", None),
-                           v_scale=getattr(past_kv, "v_scale", None))
+            if not paged_fused:
+                paged_kv_write(k, v, past_kv.k_pool, past_kv.v_pool,
+                               past_kv.block_table, past_kv.pos_t,
+                               k_scale=getattr(past_kv, "k_scale", None),
+                               v_scale=getattr(past_kv, "v_scale", None))
             present = past_kv
         elif past_kv is not None:
             if hasattr(past_kv, "append"):     # StaticKVCache layer

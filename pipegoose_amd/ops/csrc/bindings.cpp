@@ -69,6 +69,19 @@ torch::Tensor paged_prefill_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
                                      torch::Tensor block_table,
                                      torch::Tensor slopes, double scale,
                                      torch::Tensor start);
+torch::Tensor paged_rope_write(torch::Tensor q, torch::Tensor k_new,
+                               torch::Tensor v_new, torch::Tensor k_pool,
+                               torch::Tensor v_pool,
+                               torch::Tensor block_table, torch::Tensor start,
+                               double theta, torch::Tensor freq_tab);
+torch::Tensor paged_rope_write_fp8(torch::Tensor q, torch::Tensor k_new,
+                                   torch::Tensor v_new, torch::Tensor k_pool,
+                                   torch::Tensor v_pool,
+                                   torch::Tensor k_scale,
+                                   torch::Tensor v_scale,
+                                   torch::Tensor block_table,
+                                   torch::Tensor start, double theta,
+                                   torch::Tensor freq_tab);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -206,6 +219,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
           py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
           py::arg("slopes"), py::arg("scale"), py::arg("start"));
+    m.def("paged_rope_write", &paged_rope_write,
+          "rotary embedding of q and k_new at positions start[b] + s (read "
+          "on the device) fused with paged_kv_write of the rotated K and of "
+          "V: one launch, cos/sin once per token; returns q_rot, rows outside "
+          "[0, max_pages*PAGE) dropped and zero in q_rot (gfx950)",
+          py::arg("q"), py::arg("k_new"), py::arg("v_new"),
+          py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+          py::arg("start"), py::arg("theta"), py::arg("freq_tab"));
+    m.def("paged_rope_write_fp8", &paged_rope_write_fp8,
+          "paged_rope_write into e4m3fn pools: the rotated K row, rounded to "
+          "bf16, and the V row are quantised as paged_kv_write_fp8 does "
+          "(gfx950)",
+          py::arg("q"), py::arg("k_new"), py::arg("v_new"),
+          py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"),
+          py::arg("v_scale"), py::arg("block_table"), py::arg("start"),
+          py::arg("theta"), py::arg("freq_tab"));
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

@@ -61,18 +61,20 @@ def rope_at_position(x: torch.Tensor, theta_base: float,
     the decode step, ``S > 1`` a prefill chunk behind a cached prefix."""
     half = x.size(-1) // 2
     S = x.size(2)
-    d = torch.arange(half, device=x.device, dtype=torch.float32)
+    # fp32 arithmetic, as the kernels; fp64 in gives the fp64 oracle
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    d = torch.arange(half, device=x.device, dtype=ct)
     freqs = theta_base ** (-2.0 * d / x.size(-1))
     if S == 1:
-        ang = pos_t.float()[:, None] * freqs          # [1 or B, half]
+        ang = pos_t.to(ct)[:, None] * freqs           # [1 or B, half]
         cos, sin = ang.cos(), ang.sin()
         if pos_t.numel() > 1:                         # per row: [B, 1, 1, half]
             cos, sin = cos[:, None, None, :], sin[:, None, None, :]
     else:
         pos = pos_t[:, None] + torch.arange(S, device=x.device)
-        ang = pos.float()[:, :, None] * freqs         # [1 or B, S, half]
+        ang = pos.to(ct)[:, :, None] * freqs          # [1 or B, S, half]
         cos, sin = ang.cos()[:, None], ang.sin()[:, None]
-    x1, x2 = x[..., :half].float(), x[..., half:].float()
+    x1, x2 = x[..., :half].to(ct), x[..., half:].to(ct)
     y1 = x1 * cos - x2 * sin
     y2 = x2 * cos + x1 * sin
     return torch.cat([y1, y2], dim=-1).to(x.dtype)
