@@ -173,6 +173,28 @@ class BloomAttention(nn.Module):
         k = fused[..., 1, :].transpose(1, 2)
         v = fused[..., 2, :].transpose(1, 2)
 
+        if getattr(past_kv, "packed", False):
+            # token-packed ragged batch (kv_cache.PagedPacked): ids [1, T].
+            # The new rows go through the write kernel in its per-token view
+            # (B = T, S = 1: every token its own position and table row),
+            # then ONE attention launch over all sequences reads everything
+            # from the pools, a first chunk at position 0 included
+            from pipegoose_amd.ops.paged_attention import (
+                paged_kv_write, paged_varlen_attention)
+            assert B == 1 and S == past_kv.tok_pos.numel() <= 65535, (B, S)
+            tok = fused[0]                     # [T, H, 3, hd]
+            paged_kv_write(tok[:, :, 1, None], tok[:, :, 2, None],
+                           past_kv.k_pool, past_kv.v_pool, past_kv.tok_table,
+                           past_kv.tok_pos, k_scale=past_kv.k_scale,
+                           v_scale=past_kv.v_scale)
+            out = paged_varlen_attention(
+                tok[:, :, 0], past_kv.k_pool, past_kv.v_pool,
+                past_kv.block_table, self._slopes_f32(hidden.device),
+                self.inv_norm, past_kv.cu_q, past_kv.start,
+                k_scale=past_kv.k_scale, v_scale=past_kv.v_scale)
+            out = self.dense(out.reshape(1, S, self.num_heads * self.head_dim))
+            return (out, past_kv) if use_cache else out
+
         present = None
         paged = getattr(past_kv, "paged", False)
         if paged:

@@ -209,6 +209,88 @@ class PagedRows:
                 f"slot {slot} ran past its allocated pages"
 
 
+class PagedPackedLayerView:
+    """What ``past[i]`` is for a token-packed forward (``PagedPacked``): one
+    layer's pools plus the forward's shared index tensors.  ``packed = True``
+    selects the packed branch of the attentions."""
+    packed = True
+
+    def __init__(self, k_pool, v_pool, k_scale, v_scale, rows: "PagedPacked"):
+        self.k_pool, self.v_pool = k_pool, v_pool
+        self.k_scale, self.v_scale = k_scale, v_scale
+        self.cu_q, self.start = rows.cu_q, rows.start
+        self.block_table = rows.block_table
+        self.tok_pos, self.tok_table = rows.tok_pos, rows.tok_table
+
+
+class PagedPacked:
+    """The ``past=`` object for ONE forward ``ids [1, T]`` that packs the next
+    ``lens[i]`` tokens of slot ``slots[i]`` back to back, ``T = sum(lens)``
+    (ragged batched prefill, models/paged_decode.py).  Built once per forward
+    and shared by all layers:
+
+    - ``cu_q`` int32 [B+1], the packed row ranges; ``start`` int64 [B], the
+      slots' ``pos_t``; ``block_table`` [B, max_pages], the slots' table rows
+      (what ``paged_varlen_attention`` takes);
+    - ``tok_pos`` int64 [T] and ``tok_table`` int32 [T, max_pages], every
+      token's own position and table row: the per-token view (``B = T``,
+      ``S = 1``) in which ``paged_kv_write`` / ``paged_rope_write`` write the
+      new rows.
+
+    The tensors are copies (gathers), so the slots need not be contiguous;
+    ``advance()`` moves the cache's positions after the forward."""
+    MAX_TOKENS = 65535          # the write kernels' grids hold one token each
+
+    def __init__(self, cache: "PagedKVCache", slots: List[int],
+                 lens: List[int]):
+        assert len(slots) == len(lens) >= 1 and len(set(slots)) == len(slots)
+        assert all(0 <= s < cache.max_seqs for s in slots), slots
+        assert all(n >= 0 for n in lens), lens
+        T = sum(lens)
+        assert 1 <= T <= self.MAX_TOKENS, (
+            f"a packed forward holds 1..{self.MAX_TOKENS} tokens, got {T}")
+        # rows written past a slot's pages would land in the null page and
+        # be read back as if they were the sequence
+        for slot, n in zip(slots, lens):
+            room = len(cache.pages[slot]) * cache.page_size
+            assert cache.filled[slot] + n <= room, (
+                f"packed prefill of {n} tokens runs past the pages of slot "
+                f"{slot} ({cache.filled[slot]} tokens held, pages for "
+                f"{room}): allocate() first")
+        self.cache, self.slots, self.lens = cache, list(slots), list(lens)
+        device = cache.pos_t.device
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + n)
+        seq = torch.repeat_interleave(torch.arange(len(lens)),
+                                      torch.tensor(lens)).to(device)
+        self._idx = torch.tensor(slots, device=device)
+        self._lens_t = torch.tensor(lens, device=device)
+        self.cu_q = torch.tensor(cu, dtype=torch.int32, device=device)
+        self.start = cache.pos_t[self._idx]
+        self.block_table = cache.block_table[self._idx]
+        self.tok_pos = self.start[seq] + (
+            torch.arange(T, device=device) - self.cu_q[:-1].long()[seq])
+        self.tok_table = self.block_table[seq]
+        self.layers = [PagedPackedLayerView(k, v, ks, vs, self)
+                       for k, v, ks, vs in zip(cache.k_pools, cache.v_pools,
+                                               cache.k_scales, cache.v_scales)]
+
+    def __getitem__(self, i: int) -> PagedPackedLayerView:
+        return self.layers[i]
+
+    def __len__(self):
+        return len(self.layers)
+
+    def advance(self):
+        """The forward just run wrote ``lens[i]`` tokens into ``slots[i]``:
+        move the device positions and the host mirror."""
+        cache = self.cache
+        cache.pos_t.index_add_(0, self._idx, self._lens_t)
+        for slot, n in zip(self.slots, self.lens):
+            cache.filled[slot] += n
+
+
 class PagedKVCache:
     """Paged cache bank: per layer one K and one V pool
     ``[n_pages, Hkv, page_size, D]`` shared by all sequences; one int32
@@ -335,3 +417,8 @@ class PagedKVCache:
 
     def rows(self, lo: int, hi: int) -> PagedRows:
         return PagedRows(self, lo, hi)
+
+    def packed(self, slots: List[int], lens: List[int]) -> PagedPacked:
+        """``past=`` for one token-packed forward over ``lens[i]`` new tokens
+        of ``slots[i]``."""
+        return PagedPacked(self, slots, lens)

@@ -121,6 +121,30 @@ class LlamaAttention(nn.Module):
         S = q.size(1)
         k = self.k_proj(hidden)
         v = self.v_proj(hidden)
+        if getattr(past_kv, "packed", False):
+            # token-packed ragged batch (kv_cache.PagedPacked): ids [1, T].
+            # RoPE and the cache write run in their per-token view (B = T,
+            # S = 1: every token its own position and table row), then ONE
+            # attention launch over all sequences reads everything from the
+            # pools, a first chunk at position 0 included
+            from pipegoose_amd.ops.paged_attention import (
+                paged_rope_write, paged_varlen_attention)
+            assert B == 1 and S == past_kv.tok_pos.numel() <= 65535, (B, S)
+            q = paged_rope_write(
+                q.view(S, self.num_heads, 1, self.head_dim),
+                k.view(S, self.num_kv_heads, 1, self.head_dim),
+                v.view(S, self.num_kv_heads, 1, self.head_dim),
+                past_kv.k_pool, past_kv.v_pool, past_kv.tok_table,
+                past_kv.tok_pos, self.rope_theta,
+                k_scale=past_kv.k_scale, v_scale=past_kv.v_scale)
+            out = paged_varlen_attention(
+                q[:, :, 0], past_kv.k_pool, past_kv.v_pool,
+                past_kv.block_table, self._slopes_f32(hidden.device),
+                self.inv_norm, past_kv.cu_q, past_kv.start,
+                k_scale=past_kv.k_scale, v_scale=past_kv.v_scale)
+            out = self.o_proj(
+                out.reshape(1, S, self.num_heads * self.head_dim))
+            return (out, past_kv) if use_cache else out
         q = q.view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         k = k.view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
         v = v.view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)

@@ -21,6 +21,13 @@ latency of one forward.  ``share_prefix`` lets a prompt reuse the whole pages
 of the longest token prefix it has in common with an earlier prompt of the
 same call (``PagedKVCache.fork``) and prefills only the rest.
 
+``batched_prefill=True`` prefills all prompts of a call together instead of
+one at a time: every round packs the next ``prefill_chunk`` tokens of every
+unfinished prompt (or the rest) into one forward ``ids [1, T]`` over
+``PagedKVCache.packed``, with one ragged-batch attention launch per layer
+(csrc/paged_varlen_attention.hip, profiles/paged_varlen_attn.md).  Caches in
+the model dtype only; the decode step and its graphs are the same.
+
 ``kv_dtype=torch.float8_e4m3fn`` keeps the cache in fp8 with one fp32 scale
 per cached row and kv head (csrc/paged_fp8_attention.hip): twice the tokens
 per pool byte, about half the bytes read per decode step, at e4m3 precision
@@ -36,6 +43,7 @@ from typing import List, Optional
 import torch
 
 from pipegoose_amd.distributed.parallel_mode import ParallelMode
+from pipegoose_amd.models.kv_cache import PagedPacked
 
 DEFAULT_PAGE_SIZE = 16
 
@@ -56,9 +64,17 @@ class PagedDecoder:
     def __init__(self, model, max_seqs: int, n_pages: int,
                  page_size: int = DEFAULT_PAGE_SIZE, max_len: int = 2048,
                  use_graph: Optional[bool] = None,
-                 prefill_chunk: Optional[int] = None, kv_dtype=None):
+                 prefill_chunk: Optional[int] = None, kv_dtype=None,
+                 batched_prefill: bool = False):
         assert prefill_chunk is None or prefill_chunk >= 1
         self.prefill_chunk = prefill_chunk
+        if batched_prefill and kv_dtype == torch.float8_e4m3fn:
+            raise NotImplementedError(
+                "PagedDecoder: batched_prefill needs a cache in the model "
+                "dtype: there is no fp8 ragged-batch attention kernel "
+                "(kv_dtype=torch.float8_e4m3fn prefills one prompt at a "
+                "time)")
+        self.batched_prefill = batched_prefill
         ctx = getattr(model, "parallel_context", None)
         if ctx is not None and ctx.get_world_size(ParallelMode.TENSOR) > 1:
             raise NotImplementedError(
@@ -161,6 +177,47 @@ class PagedDecoder:
         self.ids[slot].copy_(logits[0, -1].argmax(-1, keepdim=True))
 
     @torch.no_grad()
+    def _prefill_batched(self, prompts: List[torch.Tensor], shared,
+                         max_new_tokens: int):
+        """Prefill all prompts together: every round packs the next
+        ``prefill_chunk`` tokens (or the rest) of every unfinished prompt
+        into ONE forward ``ids [1, T]`` (``PagedKVCache.packed``,
+        csrc/paged_varlen_attention.hip).  A prompt that shares a prefix
+        joins once its source holds the shared tokens.  Leaves every
+        prompt's first new token in ``ids``."""
+        cache = self.cache
+        prompts = [p.to(self.device) for p in prompts]
+        done: List[Optional[int]] = [None] * len(prompts)   # None: no pages
+        step = self.prefill_chunk
+        while True:
+            for i, (src, sh) in enumerate(shared):
+                if done[i] is None and (not sh or (done[src] or 0) >= sh):
+                    if sh:
+                        cache.fork(src, i, sh)
+                    cache.allocate(i, prompts[i].numel() + max_new_tokens)
+                    done[i] = sh
+            slots, lens, room = [], [], PagedPacked.MAX_TOKENS
+            for i, p in enumerate(prompts):
+                if done[i] is not None and done[i] < p.numel() and room:
+                    n = min(p.numel() - done[i], step or room, room)
+                    slots.append(i), lens.append(n)
+                    room -= n
+            if not slots:
+                return
+            rows = cache.packed(slots, lens)
+            ids = torch.cat([prompts[i][done[i]:done[i] + n]
+                             for i, n in zip(slots, lens)])
+            logits, _ = self.model(ids[None], past=rows, use_cache=True)
+            rows.advance()
+            end = 0
+            for i, n in zip(slots, lens):
+                end += n
+                done[i] += n
+                if done[i] == prompts[i].numel():
+                    self.ids[i].copy_(
+                        logits[0, end - 1].argmax(-1, keepdim=True))
+
+    @torch.no_grad()
     def generate(self, prompts: List[torch.Tensor], max_new_tokens: int,
                  share_prefix: bool = False) -> List[torch.Tensor]:
         n = len(prompts)
@@ -190,13 +247,16 @@ class PagedDecoder:
                     f"{cache.n_free_pages} of {cache.n_pages - 1} are free")
 
             # prefill each prompt alone into its slot, behind the pages it
-            # shares with an earlier one
-            for i, prompt in enumerate(prompts):
-                src, sh = shared[i]
-                if sh:
-                    cache.fork(src, i, sh)
-                cache.allocate(i, prompt.numel() + max_new_tokens)
-                self._prefill(i, prompt, done=sh)
+            # shares with an earlier one — or all of them together
+            if self.batched_prefill:
+                self._prefill_batched(prompts, shared, max_new_tokens)
+            else:
+                for i, prompt in enumerate(prompts):
+                    src, sh = shared[i]
+                    if sh:
+                        cache.fork(src, i, sh)
+                    cache.allocate(i, prompt.numel() + max_new_tokens)
+                    self._prefill(i, prompt, done=sh)
 
             tokens = [self.ids[:n].clone()]
             remaining = max_new_tokens - 1

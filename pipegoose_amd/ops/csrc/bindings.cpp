@@ -51,6 +51,11 @@ torch::Tensor paged_prefill_attn(torch::Tensor q, torch::Tensor k_pool,
                                  torch::Tensor block_table,
                                  torch::Tensor slopes, double scale,
                                  torch::Tensor start);
+torch::Tensor paged_varlen_attn(torch::Tensor q, torch::Tensor k_pool,
+                                torch::Tensor v_pool,
+                                torch::Tensor block_table,
+                                torch::Tensor slopes, double scale,
+                                torch::Tensor cu_q, torch::Tensor start);
 torch::Tensor paged_decode_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
                                     torch::Tensor v_pool,
                                     torch::Tensor k_scale,
@@ -197,6 +202,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
           py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
           py::arg("start"));
+    m.def("paged_varlen_attn", &paged_varlen_attn,
+          "causal attention of a token-packed ragged batch q [T, H, D] over a "
+          "paged cache: sequence b owns rows cu_q[b] .. cu_q[b+1]-1 at "
+          "positions start[b] + i (both read on the device); one launch, the "
+          "GQA group shares each staged K/V tile; padding rows and rows "
+          "outside [0, max_pages*PAGE) give zeros (gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
+          py::arg("cu_q"), py::arg("start"));
     m.def("paged_decode_attn_fp8", &paged_decode_attn_fp8,
           "paged_decode_attn over e4m3fn pools with fp32 scales "
           "[n_pages, Hkv, PAGE] per cached row and kv head; same plan, "

@@ -18,6 +18,12 @@ outside ``[0, max_pages * PAGE)`` giving zeros.  Everything else (CPU, fp32,
 other head dims, ``PG_DECODE_ATTN=0``) runs the pure-torch references.
 Inference only — there is no backward.
 
+``paged_varlen_attn`` of csrc/paged_varlen_attention.hip is the same
+attention over a TOKEN-PACKED ragged batch ``q`` [T,H,D]: sequence ``b`` owns
+the rows ``cu_q[b] .. cu_q[b+1]-1`` at positions ``start[b] + i`` over
+``block_table[b]``, all read on the device, in one launch whose M tiles hold
+``64/G`` tokens x the ``G`` heads of one kv head (bf16 caches only).
+
 fp8 cache (``k_scale`` / ``v_scale`` given): the pools are
 ``torch.float8_e4m3fn`` and every cached row of every kv head has an fp32
 scale in ``[n_pages, Hkv, PAGE]`` tensors indexed by the same page ids; a row
@@ -122,6 +128,31 @@ def paged_prefill_attention_reference(q, k_pool, v_pool, block_table, slopes,
     vv = v.masked_fill((j[None, :] > p_max[:, None])[:, None, :, None], 0)
     o = torch.einsum("bkgij,bkjd->bkgid", w, vv)
     return o.reshape(B, H, Sq, D)
+
+
+def paged_varlen_attention_reference(q, k_pool, v_pool, block_table, slopes,
+                                     scale, cu_q, start, k_scale=None,
+                                     v_scale=None):
+    """Pure-torch definition of attention over a token-packed ragged batch,
+    in the dtype of ``q`` (fp64 in, fp64 oracle out):
+    ``paged_prefill_attention_reference`` applied per sequence.
+
+    q [T,H,D]; sequence ``b`` owns the packed rows ``cu_q[b] .. cu_q[b+1]-1``,
+    its row ``i`` sits at ``start[b] + i`` and sees the keys of
+    ``block_table[b]``.  Rows ``t >= cu_q[B]`` are padding and give zeros.
+    Returns [T,H,D]."""
+    cu = cu_q.tolist()
+    B = len(cu) - 1
+    st = start.to(device=q.device, dtype=torch.long).reshape(-1).expand(B)
+    o = torch.zeros_like(q)
+    for b in range(B):
+        if cu[b + 1] > cu[b]:
+            rows = slice(cu[b], cu[b + 1])
+            o[rows] = paged_prefill_attention_reference(
+                q[rows].transpose(0, 1)[None], k_pool, v_pool,
+                block_table[b:b + 1], slopes, scale, st[b:b + 1], k_scale,
+                v_scale)[0].transpose(0, 1)
+    return o
 
 
 def paged_kv_write_reference(k_new, v_new, k_pool, v_pool, block_table, start):
@@ -333,6 +364,36 @@ def paged_prefill_attention(q, k_pool, v_pool, block_table, slopes, scale,
     return ext.paged_prefill_attn(
         q, k_pool, v_pool, block_table,
         slopes.to(device=q.device, dtype=torch.float32), scale, start)
+
+
+def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
+                           cu_q, start, k_scale=None, v_scale=None):
+    """Attention of a token-packed ragged batch ``q`` [T,H,D] over the pools,
+    which already hold the rows' own K/V: sequence ``b`` owns the rows
+    ``cu_q[b] .. cu_q[b+1]-1`` (int32 [B+1]) at positions ``start[b] + i``
+    (int64 [B]) over ``block_table[b]``; rows ``t >= cu_q[B]`` give zeros.
+    One launch of ``paged_varlen_attn`` (csrc/paged_varlen_attention.hip, the
+    GQA group sharing each staged K/V tile) when ``paged_kernel_supported``,
+    else the reference.  Returns [T,H,D].
+
+    With ``k_scale`` / ``v_scale`` (fp8 cache) it runs the reference on the
+    dequantised gather: there is no fp8 varlen kernel.
+
+    Measured (profiles/paged_varlen_attn.md): 0.39-0.65x the time of the
+    eight B = 1 ``paged_prefill_attn`` launches it replaces on 8 ragged
+    prompts (spreads <= 5 %).  It is NOT the faster kernel for an
+    equal-length batch without a GQA group (1.01-1.05x
+    ``paged_prefill_attn``) or for length-1 rows behind a context (2.0-2.3x
+    ``paged_decode_attn``); callers keep those on their kernels."""
+    _inference_only("paged_varlen_attention", (q, k_pool, v_pool, slopes))
+    if _check_scales("paged_varlen_attention", k_pool, k_scale, v_scale) \
+            or not paged_kernel_supported(q[None], k_pool):
+        return paged_varlen_attention_reference(
+            q, k_pool, v_pool, block_table, slopes, scale, cu_q, start,
+            k_scale, v_scale)
+    return get_extension(required=True).paged_varlen_attn(
+        q, k_pool, v_pool, block_table,
+        slopes.to(device=q.device, dtype=torch.float32), scale, cu_q, start)
 
 
 def paged_kv_write(k_new, v_new, k_pool, v_pool, block_table, start,
