@@ -25,8 +25,13 @@ same call (``PagedKVCache.fork``) and prefills only the rest.
 one at a time: every round packs the next ``prefill_chunk`` tokens of every
 unfinished prompt (or the rest) into one forward ``ids [1, T]`` over
 ``PagedKVCache.packed``, with one ragged-batch attention launch per layer
-(csrc/paged_varlen_attention.hip, profiles/paged_varlen_attn.md).  Caches in
-the model dtype only; the decode step and its graphs are the same.
+(csrc/paged_varlen_attention.hip, profiles/paged_varlen_attn.md; over an fp8
+cache csrc/paged_fp8_varlen_attention.hip, profiles/paged_fp8_varlen_attn.md).
+With an fp8 cache it needs the fp8 kernels (``paged_fp8_kernel_supported``: a
+bf16 model on the GPU, head dim 64 or 128, a page size of 16/32/64/128, the
+extension, ``PG_DECODE_ATTN != "0"``) and is refused elsewhere, where the
+packed forward would run the pure-torch reference over the dequantised cache
+at full capacity.  The decode step and its graphs are the same.
 
 ``kv_dtype=torch.float8_e4m3fn`` keeps the cache in fp8 with one fp32 scale
 per cached row and kv head (csrc/paged_fp8_attention.hip): twice the tokens
@@ -44,6 +49,7 @@ import torch
 
 from pipegoose_amd.distributed.parallel_mode import ParallelMode
 from pipegoose_amd.models.kv_cache import PagedPacked
+from pipegoose_amd.ops.paged_attention import paged_fp8_kernel_supported
 
 DEFAULT_PAGE_SIZE = 16
 
@@ -68,12 +74,6 @@ class PagedDecoder:
                  batched_prefill: bool = False):
         assert prefill_chunk is None or prefill_chunk >= 1
         self.prefill_chunk = prefill_chunk
-        if batched_prefill and kv_dtype == torch.float8_e4m3fn:
-            raise NotImplementedError(
-                "PagedDecoder: batched_prefill needs a cache in the model "
-                "dtype: there is no fp8 ragged-batch attention kernel "
-                "(kv_dtype=torch.float8_e4m3fn prefills one prompt at a "
-                "time)")
         self.batched_prefill = batched_prefill
         ctx = getattr(model, "parallel_context", None)
         if ctx is not None and ctx.get_world_size(ParallelMode.TENSOR) > 1:
@@ -85,6 +85,18 @@ class PagedDecoder:
         self.device = p.device
         self.cache = model.new_paged_kv_cache(max_seqs, n_pages, page_size,
                                               max_len, kv_dtype=kv_dtype)
+        if batched_prefill and kv_dtype == torch.float8_e4m3fn:
+            pool = self.cache.k_pools[0]
+            q = torch.empty(1, 1, 1, pool.size(-1), dtype=p.dtype,
+                            device=p.device)
+            if not paged_fp8_kernel_supported(q, pool):
+                raise NotImplementedError(
+                    "PagedDecoder: batched_prefill over an fp8 cache needs "
+                    "the fp8 ragged-batch attention kernel (a bf16 model on "
+                    "the GPU, head dim 64 or 128, page size 16/32/64/128, "
+                    "the HIP extension, PG_DECODE_ATTN != 0); elsewhere "
+                    "kv_dtype=torch.float8_e4m3fn prefills one prompt at a "
+                    "time")
         self.ids = torch.zeros(max_seqs, 1, dtype=torch.long,
                                device=self.device)
         self.use_graph = (p.device.type == "cuda") if use_graph is None \

@@ -74,6 +74,13 @@ torch::Tensor paged_prefill_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
                                      torch::Tensor block_table,
                                      torch::Tensor slopes, double scale,
                                      torch::Tensor start);
+torch::Tensor paged_varlen_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
+                                    torch::Tensor v_pool,
+                                    torch::Tensor k_scale,
+                                    torch::Tensor v_scale,
+                                    torch::Tensor block_table,
+                                    torch::Tensor slopes, double scale,
+                                    torch::Tensor cu_q, torch::Tensor start);
 torch::Tensor paged_rope_write(torch::Tensor q, torch::Tensor k_new,
                                torch::Tensor v_new, torch::Tensor k_pool,
                                torch::Tensor v_pool,
@@ -233,6 +240,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
           py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
           py::arg("slopes"), py::arg("scale"), py::arg("start"));
+    m.def("paged_varlen_attn_fp8", &paged_varlen_attn_fp8,
+          "paged_varlen_attn over e4m3fn pools with fp32 scales "
+          "[n_pages, Hkv, PAGE] per cached row and kv head; same contract "
+          "and bf16 output, one byte-to-bf16 conversion of each K/V tile per "
+          "GQA group, no scale beyond the last visible row read (gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+          py::arg("slopes"), py::arg("scale"), py::arg("cu_q"),
+          py::arg("start"));
     m.def("paged_rope_write", &paged_rope_write,
           "rotary embedding of q and k_new at positions start[b] + s (read "
           "on the device) fused with paged_kv_write of the rotated K and of "

@@ -22,7 +22,7 @@ Inference only — there is no backward.
 attention over a TOKEN-PACKED ragged batch ``q`` [T,H,D]: sequence ``b`` owns
 the rows ``cu_q[b] .. cu_q[b+1]-1`` at positions ``start[b] + i`` over
 ``block_table[b]``, all read on the device, in one launch whose M tiles hold
-``64/G`` tokens x the ``G`` heads of one kv head (bf16 caches only).
+``64/G`` tokens x the ``G`` heads of one kv head.
 
 fp8 cache (``k_scale`` / ``v_scale`` given): the pools are
 ``torch.float8_e4m3fn`` and every cached row of every kv head has an fp32
@@ -30,9 +30,11 @@ scale in ``[n_pages, Hkv, PAGE]`` tensors indexed by the same page ids; a row
 is quantised when it is written (``scale = amax / 448``, no calibration) and
 reads back as ``float(byte) * scale``.  GPU path: ``paged_kv_write_fp8`` and
 ``paged_decode_attn_fp8`` of csrc/paged_fp8_attention.hip and
-``paged_prefill_attn_fp8`` of csrc/paged_fp8_prefill_attention.hip, under
-the same conditions and rules as the bf16 kernels; no scale beyond the last
-visible row is read either.
+``paged_prefill_attn_fp8`` of csrc/paged_fp8_prefill_attention.hip and, for
+the token-packed batch, ``paged_varlen_attn_fp8`` of
+csrc/paged_fp8_varlen_attention.hip (each K/V tile converted from bytes once
+per GQA group), under the same conditions and rules as the bf16 kernels; no
+scale beyond the last visible row is read either.
 
 ``paged_rope_write`` is the LLaMA step's rotary embedding fused with the
 cache write: q and the new K rows rotated at ``start[b] + s`` (half-split
@@ -376,8 +378,11 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
     GQA group sharing each staged K/V tile) when ``paged_kernel_supported``,
     else the reference.  Returns [T,H,D].
 
-    With ``k_scale`` / ``v_scale`` (fp8 cache) it runs the reference on the
-    dequantised gather: there is no fp8 varlen kernel.
+    With ``k_scale`` / ``v_scale`` the pools are an fp8 cache: one launch of
+    ``paged_varlen_attn_fp8`` (csrc/paged_fp8_varlen_attention.hip) when
+    ``paged_fp8_kernel_supported``, else the reference on the dequantised
+    gather, in the dtype of ``q``.  Not gated on speed, as stated there
+    (measured: profiles/paged_fp8_varlen_attn.md).
 
     Measured (profiles/paged_varlen_attn.md): 0.39-0.65x the time of the
     eight B = 1 ``paged_prefill_attn`` launches it replaces on 8 ragged
@@ -386,11 +391,18 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
     ``paged_prefill_attn``) or for length-1 rows behind a context (2.0-2.3x
     ``paged_decode_attn``); callers keep those on their kernels."""
     _inference_only("paged_varlen_attention", (q, k_pool, v_pool, slopes))
-    if _check_scales("paged_varlen_attention", k_pool, k_scale, v_scale) \
-            or not paged_kernel_supported(q[None], k_pool):
+    if _check_scales("paged_varlen_attention", k_pool, k_scale, v_scale):
+        if not paged_fp8_kernel_supported(q[None], k_pool):
+            return paged_varlen_attention_reference(
+                q, k_pool, v_pool, block_table, slopes, scale, cu_q, start,
+                k_scale, v_scale)
+        return get_extension(required=True).paged_varlen_attn_fp8(
+            q, k_pool, v_pool, k_scale, v_scale, block_table,
+            slopes.to(device=q.device, dtype=torch.float32), scale, cu_q,
+            start)
+    if not paged_kernel_supported(q[None], k_pool):
         return paged_varlen_attention_reference(
-            q, k_pool, v_pool, block_table, slopes, scale, cu_q, start,
-            k_scale, v_scale)
+            q, k_pool, v_pool, block_table, slopes, scale, cu_q, start)
     return get_extension(required=True).paged_varlen_attn(
         q, k_pool, v_pool, block_table,
         slopes.to(device=q.device, dtype=torch.float32), scale, cu_q, start)

@@ -24,6 +24,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/paged_varlen_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_prefill_attention.hip",
+    "pipegoose_amd/ops/csrc/paged_fp8_varlen_attention.hip",
     "pipegoose_amd/ops/csrc/paged_rope_write.hip",
     "pipegoose_amd/ops/csrc/probes.hip",
     "pipegoose_amd/ops/csrc/rms_norm.hip",

@@ -6,6 +6,7 @@ timing method, every comparison alternated in one process.
 Usage (GPU box): python tools/paged_varlen_attn_bench.py [--mode ragged equal decode]
                      [--context 0 1024] [--page 16]
                  python tools/paged_varlen_attn_bench.py --mode e2e
+                 python tools/paged_varlen_attn_bench.py --kv fp8 [--mode ragged | e2e]
 
 Three head shapes: bloom-560m (H16, D64, ALiBi), llama-7b (H32, D128) and a
 GQA shape (H32 over 8 kv heads, D128); 8 sequences; every sequence's rows sit
@@ -29,6 +30,14 @@ End to end (``--mode e2e``): bloom-560m, the 8 ragged prompts through
 ``PagedDecoder.generate`` to the first token, with and without
 ``batched_prefill``, host clock around a device synchronise.
 
+fp8 caches (``--kv fp8``, ops/csrc/paged_fp8_varlen_attention.hip): the
+ragged rows over e4m3fn pools with per-row scales, ONE
+``paged_varlen_attn_fp8`` launch against the loop of eight B = 1
+``paged_prefill_attn_fp8`` launches and against the bf16 ``paged_varlen_attn``
+on the same rows, all three alternated; bloom-7b1's heads (H32, D128, ALiBi)
+stand where llama-7b's do.  ``--mode e2e`` then builds both decoders with
+``kv_dtype=torch.float8_e4m3fn``.
+
 Every shape runs in a child process of its own under ``--step-timeout``; the
 parent never opens the GPU and stops at the first child that fails.
 """
@@ -45,6 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SHAPES = {                       # H, Hkv, D, alibi
     "bloom-560m": (16, 16, 64, True),
     "llama-7b": (32, 32, 128, False),
+    "bloom-7b1": (32, 32, 128, True),
     "gqa-32q8kv": (32, 8, 128, False),
 }
 LENS = {"ragged": [64, 128, 200, 333, 512, 700, 900, 1024],
@@ -59,10 +69,25 @@ def summary(times):
              for k, t in times.items()})
 
 
-def run_shape(name, modes, contexts, page, iters, repeats, warmup):
+def alternate(paths, warmup, repeats, timed):
+    """``repeats`` timings of every path, the paths taking turns."""
+    import torch
+    for i in range(warmup):
+        for fn in paths.values():
+            fn(i)
+    torch.cuda.synchronize()
+    times = {label: [] for label in paths}
+    for _ in range(repeats):
+        for label, fn in paths.items():
+            times[label].append(timed(fn))
+    return times
+
+
+def run_shape(name, modes, contexts, page, iters, repeats, warmup, kv):
     import torch
     from pipegoose_amd.models.bloom import alibi_slopes
     from pipegoose_amd.ops import get_extension
+    from pipegoose_amd.ops.paged_attention import quantize_rows_fp8
 
     assert torch.cuda.is_available(), "paged_varlen_attn_bench needs a GPU"
     ext = get_extension(required=True)
@@ -80,6 +105,10 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
            for _ in range(n_buf)]
     vps = [torch.randn(n_pages, Hkv, page, D, device=dev).bfloat16()
            for _ in range(n_buf)]
+
+    # the same pools as the fp8 cache holds them: bytes and per-row scales
+    k8s, v8s = ([quantize_rows_fp8(p) for p in pools] if kv == "fp8" else []
+                for pools in (kps, vps))
 
     def timed(fn):
         start = torch.cuda.Event(enable_timing=True)
@@ -136,6 +165,41 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                     batch, kps[i % n_buf], vps[i % n_buf], table, slopes,
                     scale, start, 0)
 
+            def varlen_fp8(i):
+                (k8, ks), (v8, vs) = k8s[i % n_buf], v8s[i % n_buf]
+                return ext.paged_varlen_attn_fp8(q, k8, v8, ks, vs, table,
+                                                 slopes, scale, cu_q, start)
+
+            def prefill_fp8_loop(i):        # the launches alone, no cat
+                (k8, ks), (v8, vs) = k8s[i % n_buf], v8s[i % n_buf]
+                return [ext.paged_prefill_attn_fp8(
+                    per_seq[b], k8, v8, ks, vs, tables[b], slopes, scale,
+                    starts[b]) for b in range(B)]
+
+            if kv == "fp8":
+                paths = {"varlen_fp8": varlen_fp8,
+                         "prefill_fp8_x8": prefill_fp8_loop, "varlen": varlen}
+                want = torch.cat([o[0].transpose(0, 1)
+                                  for o in prefill_fp8_loop(0)]).float()
+                err = (varlen_fp8(0).float() - want).abs().max().item()
+                assert err <= 2.0 ** -5 * max(1.0, want.abs().max().item()), \
+                    f"varlen_fp8 differs from prefill_fp8_x8 by {err} at " \
+                    f"{context}"
+                times = alternate(paths, warmup, repeats, timed)
+                med, spread = summary(times)
+                print(json.dumps({
+                    "shape": name, "mode": mode, "kv": kv, "H": H, "Hkv": Hkv,
+                    "D": D, "page": page, "lens": lens, "context": context,
+                    "kv_buffers": n_buf, "us": med, "spread_pct": spread,
+                    "us_all": {k: [round(x, 1) for x in t]
+                               for k, t in times.items()},
+                    "fp8_over_prefill_x8": round(
+                        med["varlen_fp8"] / med["prefill_fp8_x8"], 3),
+                    "fp8_over_bf16": round(med["varlen_fp8"] / med["varlen"],
+                                           3),
+                    "max_abs_diff": round(err, 5)}), flush=True)
+                continue
+
             old_name, old, old_check = {
                 "ragged": ("prefill_x8", prefill_loop_timed, prefill_loop),
                 "equal": ("prefill_b8", prefill_batch, lambda i:
@@ -151,14 +215,7 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
             assert err <= 2.0 ** -5 * max(1.0, want.abs().max().item()), \
                 f"varlen differs from {old_name} by {err} at {mode}/{context}"
 
-            for i in range(warmup):
-                for fn in paths.values():
-                    fn(i)
-            torch.cuda.synchronize()
-            times = {label: [] for label in paths}
-            for _ in range(repeats):                   # alternate the paths
-                for label, fn in paths.items():
-                    times[label].append(timed(fn))
+            times = alternate(paths, warmup, repeats, timed)
             med, spread = summary(times)
             pairs = sum(n * context + n * (n + 1) // 2 for n in lens)
             print(json.dumps({
@@ -173,7 +230,7 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                 "max_abs_diff": round(err, 5)}), flush=True)
 
 
-def run_e2e(repeats):
+def run_e2e(repeats, kv):
     """bloom-560m through PagedDecoder: time to the first tokens of the 8
     ragged prompts (one new token, so no decode step runs)."""
     import torch
@@ -197,7 +254,9 @@ def run_e2e(repeats):
     n_pages = sum(-(-(n + 1) // page) for n in lens) + 1
     decs = {label: PagedDecoder(model, max_seqs=8, n_pages=n_pages,
                                 page_size=page, max_len=max(lens) + page,
-                                use_graph=False, batched_prefill=flag)
+                                use_graph=False, batched_prefill=flag,
+                                kv_dtype=torch.float8_e4m3fn
+                                if kv == "fp8" else None)
             for label, flag in (("per_prompt", False), ("batched", True))}
     first = {}
     for label, dec in decs.items():                     # warm-up
@@ -212,7 +271,7 @@ def run_e2e(repeats):
             times[label].append((time.perf_counter() - t0) * 1e3)
     med, spread = summary(times)
     print(json.dumps({
-        "model": "bloom-560m", "prompts": lens, "page": page, "ms": med,
+        "model": "bloom-560m", "kv": kv, "prompts": lens, "page": page, "ms": med,
         "spread_pct": spread,
         "ms_all": {k: [round(x, 2) for x in t] for k, t in times.items()},
         "batched_over_per_prompt": round(med["batched"] / med["per_prompt"],
@@ -224,9 +283,12 @@ def run_e2e(repeats):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", default=list(SHAPES),
-                    choices=list(SHAPES))
-    ap.add_argument("--mode", nargs="+", default=["ragged", "equal", "decode"],
+    ap.add_argument("--shapes", nargs="+", choices=list(SHAPES),
+                    help="default: bloom-560m, llama-7b (bloom-7b1 with "
+                    "--kv fp8) and gqa-32q8kv")
+    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"],
+                    help="cache dtype; fp8 takes --mode ragged or e2e")
+    ap.add_argument("--mode", nargs="+",
                     choices=["ragged", "equal", "decode", "e2e"])
     ap.add_argument("--context", type=int, nargs="+", default=[0, 1024])
     ap.add_argument("--page", type=int, default=16, choices=[16, 32, 64, 128])
@@ -237,13 +299,20 @@ def main():
                     help="seconds allowed to each child process")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    fp8 = args.kv == "fp8"
+    args.mode = args.mode or (["ragged"] if fp8
+                              else ["ragged", "equal", "decode"])
+    args.shapes = args.shapes or [
+        "bloom-560m", "bloom-7b1" if fp8 else "llama-7b", "gqa-32q8kv"]
+    assert not fp8 or args.mode in (["ragged"], ["e2e"]), \
+        "--kv fp8 takes --mode ragged or --mode e2e"
 
     if args.child == "e2e":
-        run_e2e(args.repeats)
+        run_e2e(args.repeats, args.kv)
         return
     if args.child:
         run_shape(args.child, args.mode, args.context, args.page, args.iters,
-                  args.repeats, args.warmup)
+                  args.repeats, args.warmup, args.kv)
         return
     if "e2e" in args.mode:
         assert args.mode == ["e2e"], "--mode e2e runs on its own"
@@ -254,7 +323,8 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), "--child", name,
                "--mode", *args.mode, "--context", *map(str, args.context),
                "--page", str(args.page), "--iters", str(args.iters),
-               "--repeats", str(args.repeats), "--warmup", str(args.warmup)]
+               "--repeats", str(args.repeats), "--warmup", str(args.warmup),
+               "--kv", args.kv]
         try:
             rc = subprocess.run(cmd, timeout=args.step_timeout).returncode
         except subprocess.TimeoutExpired:
