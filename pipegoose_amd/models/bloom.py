@@ -191,7 +191,8 @@ class BloomAttention(nn.Module):
                 tok[:, :, 0], past_kv.k_pool, past_kv.v_pool,
                 past_kv.block_table, self._slopes_f32(hidden.device),
                 self.inv_norm, past_kv.cu_q, past_kv.start,
-                k_scale=past_kv.k_scale, v_scale=past_kv.v_scale)
+                k_scale=past_kv.k_scale, v_scale=past_kv.v_scale,
+                n_splits=0 if past_kv.split_kv else None)
             out = self.dense(out.reshape(1, S, self.num_heads * self.head_dim))
             return (out, past_kv) if use_cache else out
 

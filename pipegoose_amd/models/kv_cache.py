@@ -212,7 +212,9 @@ class PagedRows:
 class PagedPackedLayerView:
     """What ``past[i]`` is for a token-packed forward (``PagedPacked``): one
     layer's pools plus the forward's shared index tensors.  ``packed = True``
-    selects the packed branch of the attentions."""
+    selects the packed branch of the attentions; ``split_kv`` makes that
+    branch ask for the split-KV kernel at its auto plan (a forward that holds
+    decode rows)."""
     packed = True
 
     def __init__(self, k_pool, v_pool, k_scale, v_scale, rows: "PagedPacked"):
@@ -221,6 +223,7 @@ class PagedPackedLayerView:
         self.cu_q, self.start = rows.cu_q, rows.start
         self.block_table = rows.block_table
         self.tok_pos, self.tok_table = rows.tok_pos, rows.tok_table
+        self.split_kv = rows.split_kv
 
 
 class PagedPacked:
@@ -242,7 +245,8 @@ class PagedPacked:
     MAX_TOKENS = 65535          # the write kernels' grids hold one token each
 
     def __init__(self, cache: "PagedKVCache", slots: List[int],
-                 lens: List[int]):
+                 lens: List[int], split_kv: bool = False):
+        self.split_kv = split_kv
         assert len(slots) == len(lens) >= 1 and len(set(slots)) == len(slots)
         assert all(0 <= s < cache.max_seqs for s in slots), slots
         assert all(n >= 0 for n in lens), lens
@@ -418,7 +422,10 @@ class PagedKVCache:
     def rows(self, lo: int, hi: int) -> PagedRows:
         return PagedRows(self, lo, hi)
 
-    def packed(self, slots: List[int], lens: List[int]) -> PagedPacked:
+    def packed(self, slots: List[int], lens: List[int],
+               split_kv: bool = False) -> PagedPacked:
         """``past=`` for one token-packed forward over ``lens[i]`` new tokens
-        of ``slots[i]``."""
-        return PagedPacked(self, slots, lens)
+        of ``slots[i]``.  ``split_kv`` selects the split-KV attention kernel
+        (csrc/paged_varlen_split_attention.hip): for forwards that hold
+        decode rows."""
+        return PagedPacked(self, slots, lens, split_kv)

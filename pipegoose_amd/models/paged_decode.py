@@ -41,6 +41,12 @@ shared prefixes attend over the fp8 pages in a kernel as well
 (csrc/paged_fp8_prefill_attention.hip, profiles/paged_fp8_prefill_attn.md).
 The default is the model dtype.
 
+``generate_continuous`` is continuous batching on the same cache: any number
+of prompts through ``max_seqs`` slots, every step one packed forward of the
+decoding sequences' rows and the next pieces of the prefilling ones
+(csrc/paged_varlen_split_attention.hip, profiles/paged_mixed_attn.md); eager,
+greedy, opt-in.
+
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """
 from typing import List, Optional
@@ -293,3 +299,112 @@ class PagedDecoder:
         finally:
             for i in range(n):
                 cache.free(i)
+
+    # ------------------------------------------------- continuous batching
+
+    @torch.no_grad()
+    def generate_continuous(self, prompts: List[torch.Tensor],
+                            max_new_tokens: int,
+                            token_budget: Optional[int] = None
+                            ) -> List[torch.Tensor]:
+        """Greedy decode of ANY number of prompts with at most ``max_seqs``
+        in flight: a prompt is admitted (first come, first served) as soon as
+        a slot and the pages for ``len + max_new_tokens`` are free, and a
+        sequence that holds its ``max_new_tokens`` tokens frees its slot at
+        once.  Every step is ONE packed forward of at most ``token_budget``
+        tokens (default ``PagedPacked.MAX_TOKENS``): one row for every
+        decoding sequence, in slot order, then the next piece (at most
+        ``prefill_chunk`` tokens) of every admitted sequence still
+        prefilling, in admission order.  Its attention is one launch of the
+        split-KV ragged kernel per layer
+        (csrc/paged_varlen_split_attention.hip), which serves decode rows
+        and prefill pieces alike; over an fp8 cache, which has no split
+        kernel, ``paged_varlen_attn_fp8``.  T varies from step to step, so
+        the step is eager: no graph.  Returns what ``generate`` returns;
+        ``share_prefix`` is not offered here."""
+        cache = self.cache
+        budget = PagedPacked.MAX_TOKENS if token_budget is None \
+            else token_budget
+        n = len(prompts)
+        assert n >= 1 and max_new_tokens >= 1
+        assert cache.max_seqs <= budget <= PagedPacked.MAX_TOKENS, (
+            f"token_budget must lie in [max_seqs = {cache.max_seqs}, "
+            f"{PagedPacked.MAX_TOKENS}]: every decoding sequence needs its "
+            f"row, got {budget}")
+        page = cache.page_size
+        need = []                       # pages per prompt
+        for prompt in prompts:
+            assert prompt.dim() == 1 and prompt.numel() >= 1
+            total = prompt.numel() + max_new_tokens
+            if total > cache.max_len:
+                raise RuntimeError(
+                    f"PagedKVCache: {total} tokens exceed max_len "
+                    f"{cache.max_len}")
+            need.append(-(-total // page))
+            if need[-1] > cache.n_pages - 1:
+                raise RuntimeError(
+                    f"PagedKVCache: out of pages: a prompt needs "
+                    f"{need[-1]}, the pool has {cache.n_pages - 1}")
+        self.model.eval()
+        prompts = [p.to(self.device) for p in prompts]
+        split_kv = cache.kv_dtype != torch.float8_e4m3fn
+        free_slots = [s for s in range(cache.max_seqs) if not cache.pages[s]]
+        waiting = list(range(n))
+        slot_of = {}                    # in flight: prompt -> slot,
+        done = {}                       # in admission order; tokens fed
+        outs: List[List[torch.Tensor]] = [[] for _ in range(n)]
+        try:
+            while waiting or slot_of:
+                while waiting and free_slots \
+                        and need[waiting[0]] <= cache.n_free_pages:
+                    i = waiting.pop(0)
+                    slot_of[i] = free_slots.pop(0)
+                    cache.allocate(slot_of[i],
+                                   prompts[i].numel() + max_new_tokens)
+                    done[i] = 0
+                if not slot_of:
+                    raise RuntimeError(
+                        "PagedKVCache: out of pages: nothing is in flight "
+                        f"and the next prompt needs {need[waiting[0]]} of "
+                        f"{cache.n_free_pages} free pages")
+                # decode rows in slot order, then pieces in admission order
+                seqs = sorted((i for i in slot_of
+                               if done[i] == prompts[i].numel()),
+                              key=slot_of.get)
+                lens = [1] * len(seqs)
+                pieces = [outs[i][-1] for i in seqs]
+                room = budget - len(seqs)
+                for i in slot_of:
+                    left = prompts[i].numel() - done[i]
+                    if left and room:
+                        k = min(left, self.prefill_chunk or room, room)
+                        seqs.append(i), lens.append(k)
+                        pieces.append(prompts[i][done[i]:done[i] + k])
+                        room -= k
+                rows = cache.packed([slot_of[i] for i in seqs], lens,
+                                    split_kv=split_kv)
+                logits, _ = self.model(torch.cat(pieces)[None], past=rows,
+                                       use_cache=True)
+                rows.advance()
+                # the last row of every sequence that decoded or whose piece
+                # ended its prompt
+                last, end = [], 0
+                for i, k in zip(seqs, lens):
+                    end += k
+                    done[i] = min(done[i] + k, prompts[i].numel())
+                    if done[i] == prompts[i].numel():
+                        last.append((i, end - 1))
+                if not last:
+                    continue
+                at = torch.tensor([t for _, t in last], device=self.device)
+                tokens = logits[0, at].argmax(-1)
+                for j, (i, _) in enumerate(last):
+                    outs[i].append(tokens[j:j + 1])
+                    if len(outs[i]) == max_new_tokens:
+                        cache.free(slot_of[i])
+                        free_slots.append(slot_of.pop(i))
+                        free_slots.sort()
+            return [torch.cat(o) for o in outs]
+        finally:
+            for slot in slot_of.values():
+                cache.free(slot)

@@ -1,6 +1,7 @@
 // Host-side operand checks shared by the decode and paged attention ops
 // (decode_attention.hip, paged_prefill_attention.hip,
-// paged_varlen_attention.hip, paged_fp8_attention.hip,
+// paged_varlen_attention.hip, paged_varlen_split_attention.hip,
+// paged_fp8_attention.hip,
 // paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip).
 #pragma once
 

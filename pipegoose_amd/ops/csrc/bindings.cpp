@@ -56,6 +56,15 @@ torch::Tensor paged_varlen_attn(torch::Tensor q, torch::Tensor k_pool,
                                 torch::Tensor block_table,
                                 torch::Tensor slopes, double scale,
                                 torch::Tensor cu_q, torch::Tensor start);
+torch::Tensor paged_varlen_split_attn(torch::Tensor q, torch::Tensor k_pool,
+                                      torch::Tensor v_pool,
+                                      torch::Tensor block_table,
+                                      torch::Tensor slopes, double scale,
+                                      torch::Tensor cu_q, torch::Tensor start,
+                                      int64_t n_splits, bool short_body);
+std::tuple<int64_t, int64_t> paged_varlen_split_plan(int64_t T, int64_t B,
+                                                     int64_t H, int64_t Hkv,
+                                                     int64_t capacity);
 torch::Tensor paged_decode_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
                                     torch::Tensor v_pool,
                                     torch::Tensor k_scale,
@@ -218,6 +227,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
           py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
           py::arg("cu_q"), py::arg("start"));
+    m.def("paged_varlen_split_attn", &paged_varlen_split_attn,
+          "paged_varlen_attn with split-KV: every M tile's visible keys are "
+          "divided among n_splits workgroups (0 = auto, shapes only; the "
+          "chunk is derived per tile on the device), fp32 partials merged in "
+          "split order by a combine kernel; tiles of at most 16 rows (decode "
+          "rows) run a body in which each wave takes 16 keys of every key "
+          "tile; short_body=False keeps every tile on the shared-tile body "
+          "(gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("block_table"), py::arg("slopes"), py::arg("scale"),
+          py::arg("cu_q"), py::arg("start"), py::arg("n_splits") = 0,
+          py::arg("short_body") = true);
+    m.def("paged_varlen_split_plan", &paged_varlen_split_plan,
+          "(T, B, H, Hkv, capacity) -> (n_splits, tile slots): the auto plan "
+          "of paged_varlen_split_attn; raises on unsupported shapes");
     m.def("paged_decode_attn_fp8", &paged_decode_attn_fp8,
           "paged_decode_attn over e4m3fn pools with fp32 scales "
           "[n_pages, Hkv, PAGE] per cached row and kv head; same plan, "

@@ -1,8 +1,9 @@
 // Device helpers and the split-KV plan shared by the decode attention kernels
 // (decode_attention.hip: bf16, contiguous and paged; paged_fp8_attention.hip:
 // fp8 pools) and by the fp8 prefill and varlen kernels
-// (paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip), and the
-// launcher of the combine kernel, which lives in
+// (paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip), the
+// split-KV constants of paged_varlen_split_attention.hip, and the
+// launcher of the decode combine kernel, which lives in
 // decode_attention.hip.  The design is described in that file's header.
 //
 // The device helpers use compiler builtins only (no functions of the HIP

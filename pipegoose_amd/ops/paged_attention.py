@@ -369,7 +369,8 @@ def paged_prefill_attention(q, k_pool, v_pool, block_table, slopes, scale,
 
 
 def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
-                           cu_q, start, k_scale=None, v_scale=None):
+                           cu_q, start, k_scale=None, v_scale=None,
+                           n_splits=None):
     """Attention of a token-packed ragged batch ``q`` [T,H,D] over the pools,
     which already hold the rows' own K/V: sequence ``b`` owns the rows
     ``cu_q[b] .. cu_q[b+1]-1`` (int32 [B+1]) at positions ``start[b] + i``
@@ -389,8 +390,22 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
     prompts (spreads <= 5 %).  It is NOT the faster kernel for an
     equal-length batch without a GQA group (1.01-1.05x
     ``paged_prefill_attn``) or for length-1 rows behind a context (2.0-2.3x
-    ``paged_decode_attn``); callers keep those on their kernels."""
+    ``paged_decode_attn``); callers keep those on their kernels.
+
+    ``n_splits`` (an int; ``None`` is the call above, bit for bit) selects
+    ``paged_varlen_split_attn`` (csrc/paged_varlen_split_attention.hip) when
+    ``paged_kernel_supported``: the same attention with every tile's visible
+    keys divided among ``n_splits`` workgroups (0 = the shapes-only auto
+    plan, 1..64 forced) and a body for tiles of decode rows, which is what a
+    packed forward that mixes decode rows with prefill pieces wants
+    (profiles/paged_mixed_attn.md).  Elsewhere it runs the same reference,
+    which takes no plan.  There is no fp8 split kernel: with ``k_scale`` /
+    ``v_scale`` ``n_splits`` is ignored and ``paged_varlen_attn_fp8`` runs
+    as before."""
     _inference_only("paged_varlen_attention", (q, k_pool, v_pool, slopes))
+    if n_splits is not None and not 0 <= int(n_splits) <= 64:
+        raise ValueError("paged_varlen_attention: n_splits must be None, 0 "
+                         f"(auto) or 1..64, got {n_splits}")
     if _check_scales("paged_varlen_attention", k_pool, k_scale, v_scale):
         if not paged_fp8_kernel_supported(q[None], k_pool):
             return paged_varlen_attention_reference(
@@ -403,6 +418,11 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
     if not paged_kernel_supported(q[None], k_pool):
         return paged_varlen_attention_reference(
             q, k_pool, v_pool, block_table, slopes, scale, cu_q, start)
+    if n_splits is not None:
+        return get_extension(required=True).paged_varlen_split_attn(
+            q, k_pool, v_pool, block_table,
+            slopes.to(device=q.device, dtype=torch.float32), scale, cu_q,
+            start, int(n_splits))
     return get_extension(required=True).paged_varlen_attn(
         q, k_pool, v_pool, block_table,
         slopes.to(device=q.device, dtype=torch.float32), scale, cu_q, start)

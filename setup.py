@@ -22,6 +22,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/decode_attention.hip",
     "pipegoose_amd/ops/csrc/paged_prefill_attention.hip",
     "pipegoose_amd/ops/csrc/paged_varlen_attention.hip",
+    "pipegoose_amd/ops/csrc/paged_varlen_split_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_prefill_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_varlen_attention.hip",
