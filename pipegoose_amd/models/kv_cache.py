@@ -426,6 +426,7 @@ class PagedKVCache:
                split_kv: bool = False) -> PagedPacked:
         """``past=`` for one token-packed forward over ``lens[i]`` new tokens
         of ``slots[i]``.  ``split_kv`` selects the split-KV attention kernel
-        (csrc/paged_varlen_split_attention.hip): for forwards that hold
+        (csrc/paged_varlen_split_attention.hip; for an fp8 cache
+        csrc/paged_fp8_varlen_split_attention.hip): for forwards that hold
         decode rows."""
         return PagedPacked(self, slots, lens, split_kv)

@@ -44,8 +44,9 @@ The default is the model dtype.
 ``generate_continuous`` is continuous batching on the same cache: any number
 of prompts through ``max_seqs`` slots, every step one packed forward of the
 decoding sequences' rows and the next pieces of the prefilling ones
-(csrc/paged_varlen_split_attention.hip, profiles/paged_mixed_attn.md); eager,
-greedy, opt-in.
+(csrc/paged_varlen_split_attention.hip, profiles/paged_mixed_attn.md; over an
+fp8 cache csrc/paged_fp8_varlen_split_attention.hip,
+profiles/paged_fp8_mixed_attn.md); eager, greedy, opt-in.
 
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """
@@ -317,9 +318,11 @@ class PagedDecoder:
         ``prefill_chunk`` tokens) of every admitted sequence still
         prefilling, in admission order.  Its attention is one launch of the
         split-KV ragged kernel per layer
-        (csrc/paged_varlen_split_attention.hip), which serves decode rows
-        and prefill pieces alike; over an fp8 cache, which has no split
-        kernel, ``paged_varlen_attn_fp8``.  T varies from step to step, so
+        (csrc/paged_varlen_split_attention.hip; over an fp8 cache
+        csrc/paged_fp8_varlen_split_attention.hip, measured at 0.24-0.59x
+        ``paged_varlen_attn_fp8`` on decode rows behind 1024 tokens or more,
+        profiles/paged_fp8_mixed_attn.md), which serves decode rows and
+        prefill pieces alike.  T varies from step to step, so
         the step is eager: no graph.  Returns what ``generate`` returns;
         ``share_prefix`` is not offered here."""
         cache = self.cache
@@ -347,7 +350,6 @@ class PagedDecoder:
                     f"{need[-1]}, the pool has {cache.n_pages - 1}")
         self.model.eval()
         prompts = [p.to(self.device) for p in prompts]
-        split_kv = cache.kv_dtype != torch.float8_e4m3fn
         free_slots = [s for s in range(cache.max_seqs) if not cache.pages[s]]
         waiting = list(range(n))
         slot_of = {}                    # in flight: prompt -> slot,
@@ -382,7 +384,7 @@ class PagedDecoder:
                         pieces.append(prompts[i][done[i]:done[i] + k])
                         room -= k
                 rows = cache.packed([slot_of[i] for i in seqs], lens,
-                                    split_kv=split_kv)
+                                    split_kv=True)
                 logits, _ = self.model(torch.cat(pieces)[None], past=rows,
                                        use_cache=True)
                 rows.advance()

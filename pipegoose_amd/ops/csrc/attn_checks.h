@@ -2,7 +2,8 @@
 // (decode_attention.hip, paged_prefill_attention.hip,
 // paged_varlen_attention.hip, paged_varlen_split_attention.hip,
 // paged_fp8_attention.hip,
-// paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip).
+// paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip,
+// paged_fp8_varlen_split_attention.hip).
 #pragma once
 
 #include <torch/extension.h>

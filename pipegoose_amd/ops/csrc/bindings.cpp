@@ -90,6 +90,11 @@ torch::Tensor paged_varlen_attn_fp8(torch::Tensor q, torch::Tensor k_pool,
                                     torch::Tensor block_table,
                                     torch::Tensor slopes, double scale,
                                     torch::Tensor cu_q, torch::Tensor start);
+torch::Tensor paged_varlen_split_attn_fp8(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor block_table,
+    torch::Tensor slopes, double scale, torch::Tensor cu_q,
+    torch::Tensor start, int64_t n_splits, bool short_body);
 torch::Tensor paged_rope_write(torch::Tensor q, torch::Tensor k_new,
                                torch::Tensor v_new, torch::Tensor k_pool,
                                torch::Tensor v_pool,
@@ -273,6 +278,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
           py::arg("slopes"), py::arg("scale"), py::arg("cu_q"),
           py::arg("start"));
+    m.def("paged_varlen_split_attn_fp8", &paged_varlen_split_attn_fp8,
+          "paged_varlen_split_attn over e4m3fn pools with fp32 scales "
+          "[n_pages, Hkv, PAGE]: the contract of paged_varlen_attn_fp8 with "
+          "the plan (paged_varlen_split_plan) and combine kernel of the bf16 "
+          "split kernel; tiles of at most 16 rows run a body in which each "
+          "wave converts its 16 keys of every key tile in registers; "
+          "short_body=False keeps every tile on the shared-tile body "
+          "(gfx950 MFMA)",
+          py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+          py::arg("slopes"), py::arg("scale"), py::arg("cu_q"),
+          py::arg("start"), py::arg("n_splits") = 0,
+          py::arg("short_body") = true);
     m.def("paged_rope_write", &paged_rope_write,
           "rotary embedding of q and k_new at positions start[b] + s (read "
           "on the device) fused with paged_kv_write of the rotated K and of "

@@ -2,9 +2,12 @@
 // (decode_attention.hip: bf16, contiguous and paged; paged_fp8_attention.hip:
 // fp8 pools) and by the fp8 prefill and varlen kernels
 // (paged_fp8_prefill_attention.hip, paged_fp8_varlen_attention.hip), the
-// split-KV constants of paged_varlen_split_attention.hip, and the
-// launcher of the decode combine kernel, which lives in
-// decode_attention.hip.  The design is described in that file's header.
+// split-KV constants of paged_varlen_split_attention.hip and
+// paged_fp8_varlen_split_attention.hip, the launcher of the decode combine
+// kernel, which lives in decode_attention.hip, and the host plan and combine
+// launcher of the ragged split kernels, which live in
+// paged_varlen_split_attention.hip and serve its fp8 sibling too.  The designs
+// are described in those files' headers.
 //
 // The device helpers use compiler builtins only (no functions of the HIP
 // headers), so that they inline into kernels of any target-feature set.
@@ -154,5 +157,27 @@ void launch_combine(const float* part_acc, const float* part_ml,
                     const int64_t* pos, int pos_n, int pos_scalar,
                     __hip_bfloat16* o, int64_t B, int64_t H, int64_t D,
                     int64_t Skv, const DecodePlan& plan);
+
+// ---- the ragged split-KV kernels (paged_varlen_split_attention.hip and
+// paged_fp8_varlen_split_attention.hip): one plan, one combine kernel
+constexpr int64_t MAX_WORKSPACE = (int64_t)1 << 31;   // bytes of partials
+
+struct SplitPlan {
+    int n_splits, gshift;       // grid z; log2 of the heads sharing an M tile
+    int64_t n_slot, ny;         // grid x (tile slots) and y (H >> gshift)
+};
+
+// The host plan of paged_varlen_split_attention.hip's file header: shapes
+// only.  forced = 0 is the auto plan; `op` names the caller in the errors.
+SplitPlan make_split_plan(const char* op, int64_t T, int64_t B, int64_t H,
+                          int64_t Hkv, int64_t capacity, int64_t forced);
+
+// Launches paged_varlen_split_combine_kernel<D> (same file) on the current
+// stream over the plan's (n_slot, ny) grid: partials indexed (slot, split, y,
+// tile row), cu_q read on the device, bf16 output o [T,H,D].
+void launch_split_combine(const float* part_acc, const float* part_ml,
+                          const int* cu_q, __hip_bfloat16* o,
+                          const SplitPlan& plan, int64_t T, int64_t B,
+                          int64_t H, int64_t D);
 
 }  // namespace decode_common

@@ -76,6 +76,11 @@
 //            2 waves/SIMD
 //   combine: 46 (D = 64) / 79 (D = 128) VGPRs, no LDS, 8 / 6 waves/SIMD
 // no scratch in any of them: the waves/SIMD of paged_varlen_attn.
+//
+// The host plan (make_split_plan) and the launcher of the combine kernel
+// (launch_split_combine) are declared in decode_common.h and defined below:
+// paged_fp8_varlen_split_attention.hip uses both, so the fp8 kernel has this
+// plan and this combine kernel, not copies.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -96,7 +101,8 @@ constexpr int PAD = 8;        // bf16 elements (16 B) of row padding in LDS
 constexpr int SV = 16 + PAD;  // row stride of a wave's private 16-key slices
 constexpr int MAX_SEQS = 1024;
 constexpr int MAX_TOKENS = 1 << 20;
-constexpr int64_t MAX_WORKSPACE = (int64_t)1 << 31;   // bytes
+using decode_common::MAX_WORKSPACE;
+using decode_common::SplitPlan;
 constexpr float LOG2E = 1.4426950408889634f;
 
 struct TileId {
@@ -719,21 +725,19 @@ void paged_varlen_split_combine_kernel(const float* __restrict__ part_acc,
     }
 }
 
-struct SplitPlan {
-    int n_splits, gshift;
-    int64_t n_slot, ny;
-};
+}  // namespace
+
+namespace decode_common {
 
 // The host plan of the file header: shapes only.
-SplitPlan make_split_plan(int64_t T, int64_t B, int64_t H, int64_t Hkv,
-                          int64_t capacity, int64_t forced) {
-    const char* op = "paged_varlen_split_attn";
+SplitPlan make_split_plan(const char* op, int64_t T, int64_t B, int64_t H,
+                          int64_t Hkv, int64_t capacity, int64_t forced) {
     TORCH_CHECK(T >= 1 && B >= 1 && Hkv >= 1 && H >= 1 && H % Hkv == 0 &&
                 capacity >= 1, op, ": T, B, H, Hkv and the capacity must be "
                 "positive, H a multiple of Hkv");
-    TORCH_CHECK(forced >= 0 && forced <= decode_common::MAX_SPLITS, op,
-                ": n_splits must be 0 (auto) or 1..",
-                decode_common::MAX_SPLITS, ", got ", forced);
+    TORCH_CHECK(forced >= 0 && forced <= MAX_SPLITS, op,
+                ": n_splits must be 0 (auto) or 1..", MAX_SPLITS, ", got ",
+                forced);
     // the GQA group shares a tile when it divides the 64 rows
     const int64_t G = H / Hkv;
     int gshift = 0;
@@ -743,20 +747,38 @@ SplitPlan make_split_plan(int64_t T, int64_t B, int64_t H, int64_t Hkv,
     const int64_t n_slot = (T + tpt - 1) / tpt + B, ny = H / gp;
     int64_t n = forced;
     if (n == 0) {
-        n = (decode_common::TARGET_WGS + n_slot * ny - 1) / (n_slot * ny);
-        n = std::min<int64_t>(n, std::min<int64_t>(decode_common::MAX_SPLITS,
+        n = (TARGET_WGS + n_slot * ny - 1) / (n_slot * ny);
+        n = std::min<int64_t>(n, std::min<int64_t>(MAX_SPLITS,
                                                    capacity / BLOCK_N));
         n = std::max<int64_t>(n, 1);
     }
     return {(int)n, gshift, n_slot, ny};
 }
 
-}  // namespace
+void launch_split_combine(const float* part_acc, const float* part_ml,
+                          const int* cu_q, __hip_bfloat16* o,
+                          const SplitPlan& plan, int64_t T, int64_t B,
+                          int64_t H, int64_t D) {
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const dim3 grid((unsigned)plan.n_slot, (unsigned)plan.ny);
+    auto launch = [&](auto dv_) {
+        constexpr int DV = decltype(dv_)::value;
+        hipLaunchKernelGGL((paged_varlen_split_combine_kernel<DV>), grid,
+                           dim3(NW * WAVE_SIZE), 0, stream, part_acc, part_ml,
+                           cu_q, o, plan.n_splits, (int)T, (int)B, (int)H,
+                           plan.gshift);
+    };
+    if (D == 64) launch(std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 128>{});
+}
+
+}  // namespace decode_common
 
 std::tuple<int64_t, int64_t> paged_varlen_split_plan(int64_t T, int64_t B,
                                                      int64_t H, int64_t Hkv,
                                                      int64_t capacity) {
-    const SplitPlan p = make_split_plan(T, B, H, Hkv, capacity, 0);
+    const SplitPlan p = decode_common::make_split_plan(
+        "paged_varlen_split_attn", T, B, H, Hkv, capacity, 0);
     return {p.n_splits, p.n_slot};
 }
 
@@ -795,7 +817,8 @@ torch::Tensor paged_varlen_split_attn(torch::Tensor q, torch::Tensor k_pool,
                 slopes.device() == q.device(), op,
                 ": all operands must be on the same device");
 
-    const SplitPlan plan = make_split_plan(T, B, H, Hkv, capacity, n_splits);
+    const SplitPlan plan =
+        decode_common::make_split_plan(op, T, B, H, Hkv, capacity, n_splits);
     TORCH_CHECK(plan.ny <= 65535, op, ": H must fit a grid dimension");
     const int64_t ws_rows = plan.n_slot * plan.n_splits * plan.ny * BLOCK_M;
     TORCH_CHECK(plan.n_splits == 1 || ws_rows * (D + 2) * 4 <= MAX_WORKSPACE,
@@ -837,12 +860,9 @@ torch::Tensor paged_varlen_split_attn(torch::Tensor q, torch::Tensor k_pool,
                            v_pool.stride(0), v_pool.stride(1),
                            v_pool.stride(2));
         if constexpr (SP)
-            hipLaunchKernelGGL((paged_varlen_split_combine_kernel<DV>),
-                               dim3(grid.x, grid.y), dim3(NW * WAVE_SIZE), 0,
-                               stream, acc_p, ml_p, cu_q.data_ptr<int>(),
-                               reinterpret_cast<bf16*>(o.data_ptr()),
-                               plan.n_splits, (int)T, (int)B, (int)H,
-                               plan.gshift);
+            decode_common::launch_split_combine(
+                acc_p, ml_p, cu_q.data_ptr<int>(),
+                reinterpret_cast<bf16*>(o.data_ptr()), plan, T, B, H, D);
     };
     using std::integral_constant;
     if (D == 64 && plan.n_splits == 1)

@@ -33,8 +33,10 @@ reads back as ``float(byte) * scale``.  GPU path: ``paged_kv_write_fp8`` and
 ``paged_prefill_attn_fp8`` of csrc/paged_fp8_prefill_attention.hip and, for
 the token-packed batch, ``paged_varlen_attn_fp8`` of
 csrc/paged_fp8_varlen_attention.hip (each K/V tile converted from bytes once
-per GQA group), under the same conditions and rules as the bf16 kernels; no
-scale beyond the last visible row is read either.
+per GQA group) and its split-KV form ``paged_varlen_split_attn_fp8`` of
+csrc/paged_fp8_varlen_split_attention.hip, under the same conditions and
+rules as the bf16 kernels; no scale beyond the last visible row is read
+either.
 
 ``paged_rope_write`` is the LLaMA step's rotary embedding fused with the
 cache write: q and the new K rows rotated at ``start[b] + s`` (half-split
@@ -399,9 +401,12 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
     plan, 1..64 forced) and a body for tiles of decode rows, which is what a
     packed forward that mixes decode rows with prefill pieces wants
     (profiles/paged_mixed_attn.md).  Elsewhere it runs the same reference,
-    which takes no plan.  There is no fp8 split kernel: with ``k_scale`` /
-    ``v_scale`` ``n_splits`` is ignored and ``paged_varlen_attn_fp8`` runs
-    as before."""
+    which takes no plan.  With ``k_scale`` / ``v_scale`` it selects
+    ``paged_varlen_split_attn_fp8``
+    (csrc/paged_fp8_varlen_split_attention.hip) when
+    ``paged_fp8_kernel_supported``: the same plan and combine kernel over the
+    fp8 cache, decode rows converted from bytes in registers
+    (profiles/paged_fp8_mixed_attn.md)."""
     _inference_only("paged_varlen_attention", (q, k_pool, v_pool, slopes))
     if n_splits is not None and not 0 <= int(n_splits) <= 64:
         raise ValueError("paged_varlen_attention: n_splits must be None, 0 "
@@ -411,6 +416,11 @@ def paged_varlen_attention(q, k_pool, v_pool, block_table, slopes, scale,
             return paged_varlen_attention_reference(
                 q, k_pool, v_pool, block_table, slopes, scale, cu_q, start,
                 k_scale, v_scale)
+        if n_splits is not None:
+            return get_extension(required=True).paged_varlen_split_attn_fp8(
+                q, k_pool, v_pool, k_scale, v_scale, block_table,
+                slopes.to(device=q.device, dtype=torch.float32), scale, cu_q,
+                start, int(n_splits))
         return get_extension(required=True).paged_varlen_attn_fp8(
             q, k_pool, v_pool, k_scale, v_scale, block_table,
             slopes.to(device=q.device, dtype=torch.float32), scale, cu_q,

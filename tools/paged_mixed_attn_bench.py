@@ -24,6 +24,12 @@ Usage (GPU box): python tools/paged_mixed_attn_bench.py [--mode decode mixed pre
            ``max_seqs=8`` against four ``generate(batched_prefill=True)``
            calls of 8 prompts; total time and mean time to first token
 
+``--kv fp8`` (ops/csrc/paged_fp8_varlen_split_attention.hip) runs the same
+modes over e4m3fn pools with per-row scales: ``split*`` is
+``paged_varlen_split_attn_fp8``, ``varlen`` is ``paged_varlen_attn_fp8`` (the
+route it replaces), ``decode`` is ``paged_decode_attn_fp8``, and
+``bf16_split0`` is the bf16 split kernel on the unquantised pools.
+
 Every shape runs in a child process of its own under ``--step-timeout``; the
 parent never opens the GPU and stops at the first child that fails.
 """
@@ -42,10 +48,11 @@ from tools.paged_varlen_attn_bench import (LENS, SHAPES, alternate,  # noqa: E40
 NEW = 32                        # tokens per prompt of the e2e run
 
 
-def run_shape(name, modes, contexts, page, iters, repeats, warmup):
+def run_shape(name, modes, contexts, page, iters, repeats, warmup, kv):
     import torch
     from pipegoose_amd.models.bloom import alibi_slopes
     from pipegoose_amd.ops import get_extension
+    from pipegoose_amd.ops.paged_attention import quantize_rows_fp8
 
     assert torch.cuda.is_available(), "paged_mixed_attn_bench needs a GPU"
     ext = get_extension(required=True)
@@ -66,6 +73,10 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
            for _ in range(n_buf)]
     vps = [torch.randn(n_pages, Hkv, page, D, device=dev).bfloat16()
            for _ in range(n_buf)]
+    # the same pools as the fp8 cache holds them: bytes and per-row scales
+    fp8 = kv == "fp8"
+    k8s, v8s = ([quantize_rows_fp8(p) for p in pools] if fp8 else []
+                for pools in (kps, vps))
 
     def timed(fn):
         start = torch.cuda.Event(enable_timing=True)
@@ -86,29 +97,48 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                 torch.tensor(starts, dtype=torch.long, device=dev),
                 table[:len(lens)])
 
-    def split(q, cu_q, start, tab, n, short=True):
+    def split_bf16(q, cu_q, start, tab, n, short=True):
         return lambda i: ext.paged_varlen_split_attn(
             q, kps[i % n_buf], vps[i % n_buf], tab, slopes, scale, cu_q,
             start, n, short)
 
+    def cache8(i):
+        (k8, ks), (v8, vs) = k8s[i % n_buf], v8s[i % n_buf]
+        return k8, v8, ks, vs
+
+    def split(q, cu_q, start, tab, n, short=True):
+        if not fp8:
+            return split_bf16(q, cu_q, start, tab, n, short)
+        return lambda i: ext.paged_varlen_split_attn_fp8(
+            q, *cache8(i), tab, slopes, scale, cu_q, start, n, short)
+
     def varlen(q, cu_q, start, tab):
+        if fp8:
+            return lambda i: ext.paged_varlen_attn_fp8(
+                q, *cache8(i), tab, slopes, scale, cu_q, start)
         return lambda i: ext.paged_varlen_attn(
             q, kps[i % n_buf], vps[i % n_buf], tab, slopes, scale, cu_q, start)
 
     def decode(q, start, tab):                  # q [n, H, D] as [n, H, 1, D]
         qd = q[:, None].transpose(1, 2)
+        if fp8:
+            return lambda i: ext.paged_decode_attn_fp8(
+                qd, *cache8(i), tab, slopes, scale, start, 0)
         return lambda i: ext.paged_decode_attn(
             qd, kps[i % n_buf], vps[i % n_buf], tab, slopes, scale, start, 0)
 
-    def report(mode, paths, want, extra):
-        got = {k: fn(0).float() for k, fn in paths.items() if "split" in k}
+    def report(mode, paths, want, extra, prob):
+        got = {k: fn(0).float() for k, fn in paths.items()
+               if k.startswith("split")}
+        if fp8:     # the bf16 split kernel on the unquantised pools, a column
+            paths["bf16_split0"] = split_bf16(*prob, 0)
         err = max((g - want).abs().max().item() for g in got.values())
         assert err <= 2.0 ** -5 * max(1.0, want.abs().max().item()), \
             f"{mode}: the new kernel differs from the old by {err}: {extra}"
         times = alternate(paths, warmup, repeats, timed)
         med, spread = summary(times)
         print(json.dumps(dict(
-            extra, shape=name, mode=mode, H=H, Hkv=Hkv, D=D, page=page,
+            extra, shape=name, mode=mode, kv=kv, H=H, Hkv=Hkv, D=D, page=page,
             kv_buffers=n_buf, us=med, spread_pct=spread,
             us_all={k: [round(x, 1) for x in t] for k, t in times.items()},
             max_abs_diff=round(err, 5))), flush=True)
@@ -126,7 +156,7 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                                                       False)
                 report(mode, paths, paths["varlen"](0).float(), {
                     "context": context, "auto_plan": ext.paged_varlen_split_plan(
-                        8, 8, H, Hkv, max_len)[0]})
+                        8, 8, H, Hkv, max_len)[0]}, (q, cu_q, start, tab))
         elif mode == "mixed":
             for rows in (8, 32, 64):
                 lens, starts = [512] + [1] * rows, [1024] * (rows + 1)
@@ -140,7 +170,8 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                 report(mode, paths, paths["varlen"](0).float(), {
                     "decode_rows": rows, "context": 1024,
                     "auto_plan": ext.paged_varlen_split_plan(
-                        len(q), rows + 1, H, Hkv, max_len)[0]})
+                        len(q), rows + 1, H, Hkv, max_len)[0]},
+                    (q, cu_q, start, tab))
         else:
             for context in contexts:
                 lens = LENS["ragged"]
@@ -149,15 +180,20 @@ def run_shape(name, modes, contexts, page, iters, repeats, warmup):
                 paths = {"varlen": varlen(q, cu_q, start, tab),
                          "split0": split(q, cu_q, start, tab, 0)}
                 report(mode, paths, paths["varlen"](0).float(), {
-                    "lens": lens, "context": context, "auto_plan": plan[0]})
+                    "lens": lens, "context": context, "auto_plan": plan[0]},
+                    (q, cu_q, start, tab))
 
 
-def run_e2e(repeats):
-    """bloom-560m, 32 ragged prompts, NEW tokens each."""
+def run_e2e(repeats, kv):
+    """bloom-560m, 32 ragged prompts, NEW tokens each.  With an fp8 cache a
+    third path, ``continuous_unsplit``, is ``generate_continuous`` with its
+    attention sent to ``paged_varlen_attn_fp8``, the route it took before the
+    fp8 split kernel."""
     import torch
     from pipegoose_amd import ParallelContext
     from pipegoose_amd.models.bloom import BloomConfig, BloomForCausalLM
     from pipegoose_amd.models.paged_decode import PagedDecoder
+    from pipegoose_amd.ops import get_extension
 
     assert torch.cuda.is_available(), "paged_mixed_attn_bench needs a GPU"
     for name, value in (("RANK", "0"), ("LOCAL_RANK", "0"),
@@ -175,8 +211,10 @@ def run_e2e(repeats):
                for n in lens]
     n_pages = 8 * -(-(max(lens) + NEW) // page) + 1
     args = (model, 8, n_pages, page, max(lens) + NEW + page)
-    batched = PagedDecoder(*args, prefill_chunk=chunk, batched_prefill=True)
-    cont = PagedDecoder(*args, prefill_chunk=chunk)
+    kw = dict(prefill_chunk=chunk,
+              kv_dtype=torch.float8_e4m3fn if kv == "fp8" else None)
+    batched = PagedDecoder(*args, batched_prefill=True, **kw)
+    cont = PagedDecoder(*args, **kw)
 
     budget = 8 * chunk
 
@@ -206,8 +244,20 @@ def run_e2e(repeats):
         hook.remove()
         return ends
 
+    def continuous_unsplit():
+        ext = get_extension(required=True)
+        new = ext.paged_varlen_split_attn_fp8
+        ext.paged_varlen_split_attn_fp8 = \
+            lambda *a: ext.paged_varlen_attn_fp8(*a[:-1])   # drops n_splits
+        try:
+            continuous()
+        finally:
+            ext.paged_varlen_split_attn_fp8 = new
+
     paths = {"batched_x4": batched_x4, "continuous": continuous}
-    for fn in paths.values():                   # warm-up, graph capture
+    if kv == "fp8":
+        paths["continuous_unsplit"] = continuous_unsplit
+    for fn in paths.values():                  # warm-up, graph capture
         fn()
     torch.cuda.synchronize()
     times = {k: [] for k in paths}
@@ -229,7 +279,7 @@ def run_e2e(repeats):
     assert len(ends) == first.pop(), "schedule and decoder disagree"
     ttft_c = [ends[s] for s in first]
     print(json.dumps({
-        "model": "bloom-560m", "prompts": lens, "new_tokens": NEW,
+        "model": "bloom-560m", "kv": kv, "prompts": lens, "new_tokens": NEW,
         "max_seqs": 8, "page": page, "prefill_chunk": chunk,
         "total_ms": med, "spread_pct": spread,
         "ms_all": {k: [round(x, 1) for x in t] for k, t in times.items()},
@@ -276,6 +326,9 @@ def main():
                     choices=["decode", "mixed", "prefill", "e2e"])
     ap.add_argument("--context", type=int, nargs="+",
                     default=[0, 128, 1024, 4096])
+    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"],
+                    help="cache dtype; fp8 times paged_varlen_split_attn_fp8 "
+                    "against the fp8 kernels, the bf16 split kernel a column")
     ap.add_argument("--page", type=int, default=16, choices=[16, 32, 64, 128])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
@@ -286,11 +339,11 @@ def main():
     args = ap.parse_args()
 
     if args.child == "e2e":
-        run_e2e(args.repeats)
+        run_e2e(args.repeats, args.kv)
         return
     if args.child:
         run_shape(args.child, args.mode, args.context, args.page, args.iters,
-                  args.repeats, args.warmup)
+                  args.repeats, args.warmup, args.kv)
         return
     if "e2e" in args.mode:
         assert args.mode == ["e2e"], "--mode e2e runs on its own"
@@ -300,7 +353,8 @@ def main():
     for name in jobs:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", name,
                "--mode", *args.mode, "--context", *map(str, args.context),
-               "--page", str(args.page), "--iters", str(args.iters),
+               "--kv", args.kv, "--page", str(args.page),
+               "--iters", str(args.iters),
                "--repeats", str(args.repeats), "--warmup", str(args.warmup)]
         try:
             rc = subprocess.run(cmd, timeout=args.step_timeout).returncode
