@@ -1,4 +1,5 @@
-"""Greedy / top-k sampling decode for the native model families.
+"""Greedy / temperature, top-k, top-p sampling decode for the native model
+families.
 
 Works under tensor parallelism: the LM head keeps logits vocab-sharded, so
 token selection computes the local argmax/top-k and combines across the
@@ -25,8 +26,10 @@ def generate(
     top_k: int = 0,
     parallel_context: Optional[ParallelContext] = None,
     eos_token_id: Optional[int] = None,
+    top_p: float = 1.0,
 ) -> torch.Tensor:
-    """Decode ``max_new_tokens`` tokens (greedy when temperature==0)."""
+    """Decode ``max_new_tokens`` tokens: greedy when temperature==0, else
+    sampled with temperature, top-k and top-p (ops/sampling.py)."""
     import inspect
     ctx = parallel_context or getattr(model, "parallel_context", None) \
         or ParallelContext.get_context()
@@ -34,13 +37,14 @@ def generate(
     model.eval()
     ids = input_ids
 
-    # Serving fast path: greedy tp=1 decode on GPU goes through the
-    # hipGraph-captured step (2.24x over eager, token-exact — parity tests
-    # in tests/ops/test_kernels_gpu.py).  PG_GRAPH_DECODE=0 opts out;
+    # Serving fast path: tp=1 decode on GPU, greedy or sampled, goes through
+    # the hipGraph-captured step (2.24x over eager, greedy token-exact —
+    # parity tests in tests/ops/test_kernels_gpu.py).  PG_GRAPH_DECODE=0 opts
+    # out;
     # eos early-exit stays on the eager path (the graph replays a fixed
     # step count).
     import os
-    if (temperature == 0.0 and tp <= 1 and ids.is_cuda
+    if (tp <= 1 and ids.is_cuda
             and eos_token_id is None
             and hasattr(model, "new_graph_kv_cache")
             and os.environ.get("PG_GRAPH_DECODE", "1") == "1"):
@@ -56,7 +60,8 @@ def generate(
             dec = GraphDecoder(model, batch_size=ids.size(0), max_len=need)
             dec._param_ptr = pptr  # graph bakes in weight addresses: a model
             model._pg_graph_decoder = dec  # move/reload invalidates the capture
-        new = dec.generate(ids, max_new_tokens)
+        new = dec.generate(ids, max_new_tokens, temperature=temperature,
+                           top_k=top_k, top_p=top_p)
         return torch.cat([ids, new], dim=1)
     finished = torch.zeros(ids.size(0), dtype=torch.bool, device=ids.device)
     use_cache = ("use_cache" in inspect.signature(model.forward).parameters
@@ -76,7 +81,8 @@ def generate(
                 past = presents
         else:
             logits = model(ids)  # [B, S, V_local]
-        last = logits[:, -1].float()  # [B, V_local]
+        raw = logits[:, -1]           # the model dtype: bf16 rows sample in HIP
+        last = raw.float()            # [B, V_local]
         if tp > 1:
             vshard = last.size(-1)
             rank = ctx.get_local_rank(ParallelMode.TENSOR)
@@ -95,7 +101,7 @@ def generate(
             else:
                 full = F.all_gather(last, dim=-1, parallel_context=ctx,
                                     parallel_mode=ParallelMode.TENSOR)
-                next_tok = _sample(full, temperature, top_k)
+                next_tok = _sample(full, temperature, top_k, top_p)
                 # sampling is stochastic: all TP ranks must decode the SAME
                 # token — rank 0 of the group decides
                 F.broadcast(next_tok,
@@ -104,7 +110,7 @@ def generate(
                             parallel_mode=ParallelMode.TENSOR)
         else:
             next_tok = last.argmax(dim=-1) if temperature == 0.0 \
-                else _sample(last, temperature, top_k)
+                else _sample(raw, temperature, top_k, top_p)
         if eos_token_id is not None:
             next_tok = torch.where(finished,
                                    torch.full_like(next_tok, eos_token_id),
@@ -116,10 +122,8 @@ def generate(
     return ids
 
 
-def _sample(logits: torch.Tensor, temperature: float, top_k: int) -> torch.Tensor:
-    logits = logits / max(temperature, 1e-5)
-    if top_k > 0:
-        kth = logits.topk(top_k, dim=-1).values[..., -1, None]
-        logits = logits.masked_fill(logits < kth, float("-inf"))
-    probs = torch.softmax(logits, dim=-1)
-    return torch.multinomial(probs, 1).squeeze(-1)
+def _sample(logits: torch.Tensor, temperature: float, top_k: int,
+            top_p: float = 1.0) -> torch.Tensor:
+    from pipegoose_amd.ops.sampling import sample_logits
+    u = torch.rand(logits.size(0), device=logits.device)
+    return sample_logits(logits, u, temperature, top_k, top_p)

@@ -1,18 +1,29 @@
-"""Greedy decode of a RAGGED batch over a paged KV cache.
+"""Decode of a RAGGED batch over a paged KV cache, greedy or sampled.
 
 The sibling of ``GraphDecoder`` (models/graph_decode.py) for prompts of
 different lengths: K/V live in a page pool shared by all sequences
 (``PagedKVCache``, models/kv_cache.py), every sequence has a block-table row
 and a device position of its own, and the decode step — cache write through
-the table, paged decode attention, argmax, advance — runs batched over all
-live rows with per-row positions (ops/paged_attention.py,
+the table, paged decode attention, token selection, advance — runs batched
+over all live rows with per-row positions (ops/paged_attention.py,
 csrc/decode_attention.hip).
 
 ``generate`` allocates every slot's pages for prompt + new tokens up front,
 so the step has static shapes and addresses and is captured into a hipGraph
 exactly as ``GraphDecoder._capture`` does, keyed by the number of live rows;
 CPU, ``use_graph=False`` or a failed capture step eagerly with identical
-numerics.  Greedy, tp=1.
+numerics.  tp=1.
+
+Token selection is greedy (``temperature == 0``, the default: an argmax) or
+sampled with temperature, top-k and top-p, each a scalar or one value per
+prompt (ops/sampling.py, csrc/sampling.hip).  The sampled step reads its
+parameters and its uniforms from static per-slot device buffers, so one graph
+per live-row count serves any parameters; the greedy step is a graph of its
+own and is what it was.  The uniforms of a call are drawn on the device before
+its first step, ``[steps, rows]`` from a ``torch.Generator`` (``generator``,
+or the decoder's own freshly seeded one), and copied step by step into the
+static buffer ahead of the replay: a graph run and an eager run of one seed
+give the same tokens.
 
 ``prefill_chunk`` feeds a prompt in pieces of at most that many tokens (the
 later pieces attend over the pages behind them: paged prefill attention,
@@ -46,17 +57,18 @@ of prompts through ``max_seqs`` slots, every step one packed forward of the
 decoding sequences' rows and the next pieces of the prefilling ones
 (csrc/paged_varlen_split_attention.hip, profiles/paged_mixed_attn.md; over an
 fp8 cache csrc/paged_fp8_varlen_split_attention.hip,
-profiles/paged_fp8_mixed_attn.md); eager, greedy, opt-in.
+profiles/paged_fp8_mixed_attn.md); eager, opt-in.
 
 ``DEFAULT_PAGE_SIZE`` comes from profiles/paged_decode_attn.md.
 """
-from typing import List, Optional
+from typing import List, Optional, Sequence, Union
 
 import torch
 
 from pipegoose_amd.distributed.parallel_mode import ParallelMode
 from pipegoose_amd.models.kv_cache import PagedPacked
 from pipegoose_amd.ops.paged_attention import paged_fp8_kernel_supported
+from pipegoose_amd.ops.sampling import sample_logits
 
 DEFAULT_PAGE_SIZE = 16
 
@@ -108,14 +120,57 @@ class PagedDecoder:
                                device=self.device)
         self.use_graph = (p.device.type == "cuda") if use_graph is None \
             else use_graph
-        self._graphs = {}           # live rows -> captured step
+        self._graphs = {}           # (live rows, sampled?) -> captured step
         self._graph = None          # the one generate() used last
         self._rows = {}             # live rows -> PagedRows over [0, n)
+        # what the sampled step reads, per slot
+        self._sampled = False
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._temperature = torch.zeros(max_seqs, **f32)
+        self._top_k = torch.zeros(max_seqs, dtype=torch.int32,
+                                  device=self.device)
+        self._top_p = torch.ones(max_seqs, **f32)
+        self._u = torch.zeros(max_seqs, **f32)
+        self._generator = None
 
     def _live_rows(self, n: int):
         if n not in self._rows:
             self._rows[n] = self.cache.rows(0, n)
         return self._rows[n]
+
+    # ------------------------------------------------------------- sampling
+
+    def _set_sampling(self, n: int, temperature, top_k, top_p, generator):
+        """Loads the per-prompt parameters (scalars or sequences of ``n``)
+        into device tensors of ``n`` and returns them with the generator to
+        draw from; ``_sampled`` says whether any prompt samples at all."""
+        def per_prompt(x):
+            vals = list(x) if isinstance(x, (Sequence, torch.Tensor)) \
+                else [x] * n
+            assert len(vals) == n, "one sampling parameter per prompt"
+            return [float(v) for v in vals]
+        t, k, p = map(per_prompt, (temperature, top_k, top_p))
+        self._sampled = any(v > 0 for v in t)
+        if not self._sampled:
+            return None
+        if generator is None:
+            if self._generator is None:
+                self._generator = torch.Generator(device=self.device)
+                self._generator.seed()
+            generator = self._generator
+        return (torch.tensor(t, dtype=torch.float32, device=self.device),
+                torch.tensor(k, dtype=torch.int32, device=self.device),
+                torch.tensor(p, dtype=torch.float32, device=self.device),
+                generator)
+
+    def _select(self, logits: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
+        """The next token of slots [lo, hi) from ``logits [hi - lo, V]``, as
+        [hi - lo, 1]."""
+        if not self._sampled:
+            return logits.argmax(-1, keepdim=True)
+        return sample_logits(logits, self._u[lo:hi],
+                             self._temperature[lo:hi], self._top_k[lo:hi],
+                             self._top_p[lo:hi]).unsqueeze(-1)
 
     # ------------------------------------------------------------------ step
 
@@ -126,7 +181,7 @@ class PagedDecoder:
         rows = self._live_rows(n)
         ids = self.ids[:n]
         logits, _ = self.model(ids, past=rows, use_cache=True)
-        ids.copy_(logits[:, -1].argmax(-1, keepdim=True))
+        ids.copy_(self._select(logits[:, -1], 0, n))
         rows.advance(1)
 
     @torch.no_grad()
@@ -149,7 +204,7 @@ class PagedDecoder:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):   # records, does not execute
                 self._step(n)
-            self._graphs[n] = g
+            self._graphs[n, self._sampled] = g
         except Exception:
             # capture unsupported here: permanent eager fallback
             self.use_graph = False
@@ -193,7 +248,8 @@ class PagedDecoder:
             piece = prompt[lo:lo + step]
             logits, _ = self.model(piece[None], past=rows, use_cache=True)
             rows.advance(piece.numel())
-        self.ids[slot].copy_(logits[0, -1].argmax(-1, keepdim=True))
+        self.ids[slot:slot + 1].copy_(
+            self._select(logits[:, -1], slot, slot + 1))
 
     @torch.no_grad()
     def _prefill_batched(self, prompts: List[torch.Tensor], shared,
@@ -233,17 +289,30 @@ class PagedDecoder:
                 end += n
                 done[i] += n
                 if done[i] == prompts[i].numel():
-                    self.ids[i].copy_(
-                        logits[0, end - 1].argmax(-1, keepdim=True))
+                    self.ids[i:i + 1].copy_(
+                        self._select(logits[:, end - 1], i, i + 1))
 
     @torch.no_grad()
     def generate(self, prompts: List[torch.Tensor], max_new_tokens: int,
-                 share_prefix: bool = False) -> List[torch.Tensor]:
+                 share_prefix: bool = False,
+                 temperature: Union[float, Sequence[float]] = 0.0,
+                 top_k: Union[int, Sequence[int]] = 0,
+                 top_p: Union[float, Sequence[float]] = 1.0,
+                 generator=None) -> List[torch.Tensor]:
         n = len(prompts)
         cache = self.cache
         assert 1 <= n <= cache.max_seqs, "more prompts than max_seqs"
         assert max_new_tokens >= 1
         self.model.eval()
+        sampling = self._set_sampling(n, temperature, top_k, top_p, generator)
+        uniforms = None
+        if sampling is not None:
+            self._temperature[:n].copy_(sampling[0])
+            self._top_k[:n].copy_(sampling[1])
+            self._top_p[:n].copy_(sampling[2])
+            uniforms = torch.rand(max_new_tokens, n, generator=sampling[3],
+                                  device=self.device)
+            self._u[:n].copy_(uniforms[0])
         try:
             for prompt in prompts:
                 assert prompt.dim() == 1 and prompt.numel() >= 1
@@ -279,16 +348,21 @@ class PagedDecoder:
 
             tokens = [self.ids[:n].clone()]
             remaining = max_new_tokens - 1
-            if self.use_graph and remaining > 1 and n not in self._graphs:
+            key = (n, self._sampled)
+            if self.use_graph and remaining > 1 and key not in self._graphs:
+                if uniforms is not None:
+                    self._u[:n].copy_(uniforms[1])
                 warmup_tokens = self._capture(n)
                 if warmup_tokens is not None:   # the warmup step really ran
                     tokens.append(warmup_tokens)
                     remaining -= 1
             # a captured graph replays against the CURRENT table, positions
             # and pools — no re-capture across calls
-            self._graph = self._graphs.get(n)
+            self._graph = self._graphs.get(key)
             rows = self._live_rows(n)
             for _ in range(remaining):
+                if uniforms is not None:    # async, into the static buffer
+                    self._u[:n].copy_(uniforms[len(tokens)])
                 if self._graph is not None:
                     self._graph.replay()
                     rows.host_advance(1)
@@ -306,9 +380,12 @@ class PagedDecoder:
     @torch.no_grad()
     def generate_continuous(self, prompts: List[torch.Tensor],
                             max_new_tokens: int,
-                            token_budget: Optional[int] = None
-                            ) -> List[torch.Tensor]:
-        """Greedy decode of ANY number of prompts with at most ``max_seqs``
+                            token_budget: Optional[int] = None,
+                            temperature: Union[float, Sequence[float]] = 0.0,
+                            top_k: Union[int, Sequence[int]] = 0,
+                            top_p: Union[float, Sequence[float]] = 1.0,
+                            generator=None) -> List[torch.Tensor]:
+        """Decode of ANY number of prompts with at most ``max_seqs``
         in flight: a prompt is admitted (first come, first served) as soon as
         a slot and the pages for ``len + max_new_tokens`` are free, and a
         sequence that holds its ``max_new_tokens`` tokens frees its slot at
@@ -324,7 +401,9 @@ class PagedDecoder:
         profiles/paged_fp8_mixed_attn.md), which serves decode rows and
         prefill pieces alike.  T varies from step to step, so
         the step is eager: no graph.  Returns what ``generate`` returns;
-        ``share_prefix`` is not offered here."""
+        ``share_prefix`` is not offered here.  The sampling arguments are
+        those of ``generate``; the uniforms are drawn step by step, one per
+        slot, and a sequence takes the one of the slot it was admitted to."""
         cache = self.cache
         budget = PagedPacked.MAX_TOKENS if token_budget is None \
             else token_budget
@@ -349,6 +428,7 @@ class PagedDecoder:
                     f"PagedKVCache: out of pages: a prompt needs "
                     f"{need[-1]}, the pool has {cache.n_pages - 1}")
         self.model.eval()
+        sampling = self._set_sampling(n, temperature, top_k, top_p, generator)
         prompts = [p.to(self.device) for p in prompts]
         free_slots = [s for s in range(cache.max_seqs) if not cache.pages[s]]
         waiting = list(range(n))
@@ -399,7 +479,18 @@ class PagedDecoder:
                 if not last:
                     continue
                 at = torch.tensor([t for _, t in last], device=self.device)
-                tokens = logits[0, at].argmax(-1)
+                if sampling is None:
+                    tokens = logits[0, at].argmax(-1)
+                else:
+                    who = torch.tensor([i for i, _ in last],
+                                       device=self.device)
+                    slots = torch.tensor([slot_of[i] for i, _ in last],
+                                         device=self.device)
+                    u = torch.rand(cache.max_seqs, generator=sampling[3],
+                                   device=self.device)
+                    tokens = sample_logits(logits[0, at], u[slots],
+                                           sampling[0][who], sampling[1][who],
+                                           sampling[2][who])
                 for j, (i, _) in enumerate(last):
                     outs[i].append(tokens[j:j + 1])
                     if len(outs[i]) == max_new_tokens:

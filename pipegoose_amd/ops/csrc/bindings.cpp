@@ -108,6 +108,9 @@ torch::Tensor paged_rope_write_fp8(torch::Tensor q, torch::Tensor k_new,
                                    torch::Tensor block_table,
                                    torch::Tensor start, double theta,
                                    torch::Tensor freq_tab);
+torch::Tensor sample_logits(torch::Tensor logits, torch::Tensor u,
+                            torch::Tensor temperature, torch::Tensor top_k,
+                            torch::Tensor top_p, int64_t splits);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor Bt);
 torch::Tensor tr16_probe(torch::Tensor tile);
@@ -307,6 +310,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"),
           py::arg("v_scale"), py::arg("block_table"), py::arg("start"),
           py::arg("theta"), py::arg("freq_tab"));
+    m.def("sample_logits", &sample_logits,
+          "one token per row of bf16 logits [R, V]: temperature, top-k and "
+          "top-p with per-row device parameters (temperature fp32, top_k "
+          "int32, top_p fp32, u fp32 uniforms, all [R]); T == 0 rows are the "
+          "argmax at its lowest index; two-level radix selection on 16-bit "
+          "keys, fixed-point masses, no host sync; splits = 0 is the auto "
+          "plan; returns int64 [R] (gfx950)",
+          py::arg("logits"), py::arg("u"), py::arg("temperature"),
+          py::arg("top_k"), py::arg("top_p"), py::arg("splits") = 0);
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
     m.def("mfma_probe32", &mfma_probe32,

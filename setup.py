@@ -28,6 +28,7 @@ SRC = [
     "pipegoose_amd/ops/csrc/paged_fp8_varlen_attention.hip",
     "pipegoose_amd/ops/csrc/paged_fp8_varlen_split_attention.hip",
     "pipegoose_amd/ops/csrc/paged_rope_write.hip",
+    "pipegoose_amd/ops/csrc/sampling.hip",
     "pipegoose_amd/ops/csrc/probes.hip",
     "pipegoose_amd/ops/csrc/rms_norm.hip",
     "pipegoose_amd/ops/csrc/rope.hip",
