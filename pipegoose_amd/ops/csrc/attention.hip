@@ -26,7 +26,14 @@
 // statistics are lane-local, XOR-swizzled and sub-tiled LDS images read with
 // ds_read_b64_tr_b16, double-buffered tiles, exp2 domain.  dkdv_v2 is one
 // fused kernel at D=64; at D=128 it would spill and runs as a dv-only pass
-// plus two half-width dk passes.
+// plus two half-width dk passes.  Every v2 kernel takes its (block, head,
+// batch) from its linear block id through attn_work_order.h instead of from
+// blockIdx directly: all blocks of a (head, batch) group run on one XCD (one
+// L2) when the group count is a multiple of 8, and within an XCD the blocks
+// with the most tiles under the causal mask are dispatched first (the last
+// q block for fwd and dq, the first kv block for dkdv).  The grids are
+// unchanged and the map is a bijection, so outputs are bitwise independent
+// of it.
 //
 // v1 is the fallback for S % 128 == 64, which v2's 128-row workgroups cannot
 // tile: v_mfma_f32_16x16x32_bf16, one workgroup = 4 waves x 16 rows = 64 q
@@ -39,6 +46,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "attn_work_order.h"
 #include "mfma_frag.h"
 
 // ======================================================================
@@ -284,6 +292,20 @@ __device__ __forceinline__ int swz64(int row, int elem_col) {
     return row * 64 + ((((elem_col) << 1) ^ ((row & 7) << 4)) >> 1);
 }
 
+// This workgroup's place in the v2 work order (attn_work_order.h: groups
+// pinned to an XCD, heaviest block first), decoded once at kernel entry from
+// the linear block id.  readfirstlane tells the compiler that the result is
+// wave-uniform, so the divisions leave no vector registers behind and
+// everything derived from it stays scalar.
+__device__ __forceinline__ AttnWork v2_work() {
+    const AttnWork w = attn_work_order(
+        blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z),
+        gridDim.y, gridDim.z);
+    return AttnWork{__builtin_amdgcn_readfirstlane(w.rank),
+                    __builtin_amdgcn_readfirstlane(w.h),
+                    __builtin_amdgcn_readfirstlane(w.b)};
+}
+
 template <int RS>
 __device__ __forceinline__ int swz_rm(int row, int elem_col) {
     return RS == 64 ? swz64(row, elem_col) : swz128(row, elem_col);
@@ -351,23 +373,9 @@ void attn_fwd_v2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
     __shared__ __attribute__((aligned(16))) bf16 k_lds[2][KVB * 128];
     __shared__ __attribute__((aligned(16))) bf16 vs_lds[2][KVB * D];
 
-    // XCD-affinity remap (T1): the hardware places linear block id L on XCD
-    // L%8, so with qblock fastest-varying the q-blocks sharing one (b,h)'s
-    // K/V land on 8 different L2s.  When H*B % 8 == 0, re-deriving (qblock,
-    // h, b) with (h,b) fastest pins each (b,h) group to ONE XCD, making its
-    // K/V tile L2-resident across q-blocks.  Pure speed, never correctness.
-    int qblock = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    {
-        const int ngrp = gridDim.y * gridDim.z;  // H * B
-        if ((ngrp & 7) == 0) {
-            const int flat = blockIdx.x +
-                gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            qblock = flat / ngrp;
-            const int g = flat % ngrp;
-            h = g % gridDim.y;
-            b = g / gridDim.y;
-        }
-    }
+    // the last q block loops over the most kv tiles: heaviest first
+    const AttnWork wk = v2_work();
+    const int qblock = (int)gridDim.x - 1 - wk.rank, h = wk.h, b = wk.b;
     const int tid = threadIdx.x;
     const int wave = tid / WAVE_SIZE;
     const int lane = tid % WAVE_SIZE;
@@ -1117,9 +1125,11 @@ void attn_bwd_dq_v2_kernel(const bf16* __restrict__ dout,
     __shared__ __attribute__((aligned(16))) bf16 ks_lds[2][KVB * D];
     __shared__ __attribute__((aligned(16))) bf16 v_lds[2][KVB * 128];
 
-    const int qblock = blockIdx.x;
-    const int h = blockIdx.y;
-    const int b = blockIdx.z;
+    // the last q block loops over the most kv tiles: heaviest first
+    const AttnWork wk = v2_work();
+    const int qblock = (int)gridDim.x - 1 - wk.rank;
+    const int h = wk.h;
+    const int b = wk.b;
     const int tid = threadIdx.x;
     const int wave = tid / WAVE_SIZE;
     const int lane = tid % WAVE_SIZE;
@@ -1377,9 +1387,11 @@ void attn_bwd_dkdv_v2_kernel(const bf16* __restrict__ dout,
     __shared__ __attribute__((aligned(16))) float lse_lds[2][QT];
     __shared__ __attribute__((aligned(16))) float dlt_lds[2][QT];
 
-    const int nb = blockIdx.x;
-    const int h = blockIdx.y;   // KV head
-    const int b = blockIdx.z;
+    // the first kv block is seen by the most q tiles: heaviest first
+    const AttnWork wk = v2_work();
+    const int nb = wk.rank;
+    const int h = wk.h;   // KV head
+    const int b = wk.b;
     const int tid = threadIdx.x;
     const int wave = tid / WAVE_SIZE;
     const int lane = tid % WAVE_SIZE;
